@@ -21,6 +21,15 @@ rate (numpy frames in, CPU results out) is reported separately as "host_io_fps".
 (frame, delta) flow computations of a look-ahead window of frames are sharded over the ranks
 (mft_amd/dist.py): strong scaling of one video, `value` = frames of that one video per second.
 
+A plain run does what the headline figure needs and nothing else: set-up, pre-roll, warm-up, the --steps timed steps, the
+outputs (--dump-outputs DIR) and the JSON line.  --full adds every other pass, in this order behind the timed region: the host-io
+and API-default rates, per-rank diagnostics (N > 1), the per-kernel profile pass (`kernels`, `roofline`), the other arithmetic,
+parity against the CPU oracle and the CPU baseline; the --no-* options switch single passes of a --full run off.
+
+--dump-outputs DIR writes what the caller of the timed path received for the last timed frame (`meta.result` of `track()`:
+flow, occlusion, sigma) as DIR/<name>.npy in float32; above 64 MB in all, the same seeded sample of pixels of every plane
+(DIR/pixel_index.npy holds the sampled flat pixel indices).  Frames and weights are seeded: the same arguments give the same inputs.
+
 Rank 0 prints ONE JSON line (see DESIGN.md section "Measurement").
 """
 import argparse
@@ -469,18 +478,42 @@ def respawn_under_torchrun(n):
 
 
 HOST_MS = []          # host time of every track() call (enqueue only: nothing waits for the GPU)
+LAST_META = []        # the meta of the last frame run_frames tracked: what the caller of track() received for it
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(meta, out_dir, seed=0):
+    """--dump-outputs: `meta.result` (flow (2, H, W), occlusion (1, H, W), sigma (1, H, W)) as <out_dir>/<name>.npy in float32.
+    Above DUMP_LIMIT_BYTES in all, every plane keeps the same seeded sample of pixels ((C, n), flattened per channel) and
+    pixel_index.npy holds the sampled flat indices (float64: exact).  -> names written."""
+    r = meta.result
+    arrays = {k: getattr(r, k).detach().float().cpu().numpy() for k in ("flow", "occlusion", "sigma")}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        H, W = arrays["flow"].shape[-2:]
+        chans = sum(a.shape[0] for a in arrays.values())
+        n = min(H * W, DUMP_LIMIT_BYTES // (4 * chans + 8))
+        idx = np.sort(np.random.default_rng(seed).choice(H * W, size=n, replace=False))
+        arrays = {k: a.reshape(a.shape[0], -1)[:, idx] for k, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(out / f"{k}.npy", np.ascontiguousarray(a))
+    return sorted(arrays)
 
 
 def run_frames(tracker, frames, first, count, window):
     """Track frames[first : first + count]; with `window` > 1 in look-ahead windows (multi-GPU).
-    -> pairs per frame."""
+    -> pairs per frame (the last frame's meta: LAST_META[0])."""
     pairs = []
+    meta = None
     if window <= 1:
         for i in range(first, first + count):
             t0 = time.perf_counter()
-            tracker.track(frames[i])
+            meta = tracker.track(frames[i])
             HOST_MS.append(1e3 * (time.perf_counter() - t0))
             pairs.append(len(tracker.last_pairs))
+        LAST_META[:] = [meta]
         return pairs
     # full windows of `window` frames, the remainder last (20 frames, window 8: 8 + 8 + 4): with window = world size every rank
     # gets exactly one full batch of 7 units per full window (8 x 7 units on 8 ranks); equal windows (7 + 7 + 6) round 49 / 8
@@ -496,11 +529,16 @@ def run_frames(tracker, frames, first, count, window):
         nxt = frames[i + n: i + n + nn]                              # the following window: its encoders start early
         # pipelined: the call hands back the PREVIOUS window's results; this window's result exchange and selections
         # overlap the next window's flow batches
-        got += len(tracker.track_window(frames[i: i + n], next_imgs=nxt, defer=True))
+        metas = tracker.track_window(frames[i: i + n], next_imgs=nxt, defer=True)
+        got += len(metas)
+        meta = metas[-1] if metas else meta
         pairs += [len(tracker._plan(k)) for k in range(i, i + n)]
         i += n
-    got += len(tracker.flush_window())
+    metas = tracker.flush_window()
+    got += len(metas)
+    meta = metas[-1] if metas else meta
     assert got == count, (got, count)
+    LAST_META[:] = [meta]
     return pairs
 
 
@@ -545,7 +583,16 @@ def main():
                          "spend, without the wire time of the collectives: the projected multi-GPU rate")
     ap.add_argument("--force-sharded", action="store_true",
                     help="run the multi-GPU code path (windows, RCCL all-gathers) even with one rank (testing)")
+    ap.add_argument("--full", action="store_true",
+                    help="every pass beyond the headline figure: host-io and API-default rates, per-rank diagnostics, the per-kernel "
+                         "profile (`kernels`, `roofline`), the other arithmetic, parity against the CPU oracle, the CPU baseline "
+                         "(without it: set-up, warm-up, the timed steps and the JSON line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's result (flow, occlusion, sigma: what track() handed its caller) as "
+                         "DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(respawn_under_torchrun(args.gpus))
@@ -577,12 +624,12 @@ def main():
 
     from mft_amd.synth import SyntheticVideo
     preroll = FIRST_FULL_FRAME - 1                                # untimed: frames 1 .. 32; warm-up starts at frame 33
-    n_io = 0 if (args.no_host_io or world > 1 or args.force_sharded) else max(8, args.steps)
+    n_io = 0 if (not args.full or args.no_host_io or world > 1 or args.force_sharded) else max(8, args.steps)
     IO_WARM = 8                                                   # untimed frames in front of the host-io pass
     n_io_frames = n_io + (IO_WARM if n_io else 0)
-    n_prof = 0 if args.no_profile else args.steps
+    n_prof = 0 if (not args.full or args.no_profile) else args.steps
     n_frames = 1 + preroll + args.warmup + args.steps + n_prof + n_io_frames
-    n_api = 0 if (args.no_host_io or world > 1 or args.force_sharded) else max(20, args.steps)
+    n_api = 0 if (not args.full or args.no_host_io or world > 1 or args.force_sharded) else max(20, args.steps)
     if n_api:
         n_frames = max(n_frames, FIRST_FULL_FRAME + 7 + 2 * n_api)
     vid = SyntheticVideo(args.height, args.width, n_frames=max(n_frames, 48), seed=0)
@@ -638,6 +685,10 @@ def main():
     log(f"timed region: {args.steps} steps in {dt:.3f} s, pairs/frame min {min(timed_pairs)} max {max(timed_pairs)}")
     if min(timed_pairs + warm_pairs) != FULL_PAIRS or max(timed_pairs) != FULL_PAIRS:
         raise SystemExit(f"timed region is not the 7-pair steady state: warm-up {warm_pairs}, timed {timed_pairs}")
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(LAST_META[0], args.dump_outputs)
+        log(f"outputs of frame {first + args.steps - 1} written to {args.dump_outputs}: {', '.join(names)}")
+    LAST_META.clear()
 
     host_io_fps = None
     if n_io and rank == 0:
@@ -657,6 +708,7 @@ def main():
         ones = torch.ones(1, device="cuda", dtype=torch.float32)
         dist.all_reduce(ones)
         ranks_seen = int(round(float(ones.item())))
+    if sharded and args.full:
         mine = rank_diagnostics(tracker, window, args.height, args.width, args.emulate_world or world, rank, backend)
         print("[bench rank %d] %s" % (rank, json.dumps(mine)), file=sys.stderr, flush=True)
         if world > 1:
@@ -754,7 +806,7 @@ def main():
                     algorithmic_tflops=dom["algorithmic_tflops"],
                     algorithmic_vs_fp32_mfma_peak=dom["algorithmic_tflops"] / FP32_MFMA_PEAK_TFLOPS)
             result["kernels"] = kernels
-    if not sharded and rank == 0 and not args.no_alt_arith:
+    if args.full and not sharded and rank == 0 and not args.no_alt_arith:
         # the same steady-state frames in the other arithmetic (a fresh tracker; short: 10 timed frames)
         other = "fp32" if args.arith == "split" else "split"
         alt_args = argparse.Namespace(**{**vars(args), "arith": other})
@@ -785,12 +837,13 @@ def main():
             result["host_io_fps"] = host_io_fps
             result["host_io_path"] = ("pinned frames in and pinned results out, both moved by a copy kernel (no SDMA queue); the same tracker, "
                                       "right behind the timed region")
-        torch.set_num_threads(oracle_threads())
-        if not args.no_parity:
+        if args.full:
+            torch.set_num_threads(oracle_threads())
+        if args.full and not args.no_parity:
             result["parity"] = flow_epe_vs_oracle(args, tracker, vid)
             result["parity"].update(track_parity_real_state(args, vid))
             log(f"parity vs oracle: {result.get('parity')}")
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             result["cpu_baseline"], oracle_meta = cpu_baseline(args, vid)
             log("cpu baseline done")
             if not args.no_parity:

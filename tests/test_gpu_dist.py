@@ -107,7 +107,7 @@ def test_bench_sharded_line_carries_roofline_and_ranks_seen():
     from pathlib import Path
     repo = Path(__file__).resolve().parents[1]
     env = {k: v for k, v in os.environ.items() if k not in ("MASTER_ADDR", "MASTER_PORT", "RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    out = subprocess.run([sys.executable, str(repo / "bench.py"), "--gpus", "1", "--force-sharded", "--steps", "4", "--warmup", "1",
+    out = subprocess.run([sys.executable, str(repo / "bench.py"), "--gpus", "1", "--force-sharded", "--steps", "4", "--warmup", "1", "--full",
                           "--no-cpu-baseline", "--no-parity", "--no-alt-arith"], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])
@@ -129,7 +129,7 @@ def test_bench_two_real_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("MASTER_ADDR", "MASTER_PORT", "RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(MFT_DIST_BACKEND="gloo", MFT_DIST_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", "29655", str(REPO / "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2"]
+           "--master-port", "29655", str(REPO / "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=850)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]

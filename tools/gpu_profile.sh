@@ -7,7 +7,7 @@ TAG=${1:-r3}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python bench.py --steps 20 --warmup 5"
+BENCH="python bench.py --full --steps 20 --warmup 5"
 # per-kernel passes: one batch, one stream, encoders on the main stream -> every kernel runs alone, like bench.py's own
 # HIP-event pass (the timed region of the default run overlaps two half-batches and the next frame's encoders)
 QUIET="--no-cpu-baseline --no-profile --no-parity --no-host-io --sync-encode --no-alt-arith --no-graphs --frames-in-flight 1"
@@ -28,9 +28,9 @@ fi
 (for rep in 1 2; do for f in 1 2 3; do $BENCH --no-cpu-baseline --no-parity --no-alt-arith --no-profile --frames-in-flight $f 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readlines()[-1]); print('frames in flight $f:', round(d['value'],1), 'frames/s,', round(d['ms_per_step'],3), 'ms per frame, with PCIe', round(d['host_io_fps'],1))"; done; done
  for f in 1 2; do python bench.py --steps 20 --warmup 5 --height 256 --width 256 --no-cpu-baseline --no-parity --no-alt-arith --no-profile --no-host-io --frames-in-flight $f 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readlines()[-1]); print('256 x 256, frames in flight $f:', round(d['value'],1), 'frames/s')"; done
  for f in 1 2; do python bench.py --steps 6 --warmup 2 --height 1080 --width 1920 --no-cpu-baseline --no-parity --no-alt-arith --no-profile --no-host-io --frames-in-flight $f 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readlines()[-1]); print('1080p, frames in flight $f:', round(d['value'],2), 'frames/s')"; done) > $OUT/frames_in_flight_ab.txt
-python bench.py --steps 20 --warmup 5 --height 256 --width 256 --no-cpu-baseline --no-parity --no-alt-arith > $OUT/bench_256.json 2>/dev/null
-python bench.py --steps 5 --warmup 2 --height 1080 --width 1920 --no-cpu-baseline --no-parity --no-alt-arith --no-host-io > $OUT/bench_1080p.json 2>/dev/null
-python bench.py --steps 20 --warmup 5 --force-sharded --no-cpu-baseline --no-parity --no-alt-arith > $OUT/bench_forced_sharded_x1.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 --height 256 --width 256 --no-cpu-baseline --no-parity --no-alt-arith > $OUT/bench_256.json 2>/dev/null
+python bench.py --full --steps 5 --warmup 2 --height 1080 --width 1920 --no-cpu-baseline --no-parity --no-alt-arith --no-host-io > $OUT/bench_1080p.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 --force-sharded --no-cpu-baseline --no-parity --no-alt-arith > $OUT/bench_forced_sharded_x1.json 2>/dev/null
 (for g in 2 4 8; do python bench.py --steps 20 --warmup 5 --force-sharded --emulate-world $g --no-cpu-baseline --no-parity --no-alt-arith --no-profile 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('emulated world $g (driver flags):', round(d['value'],1), 'frames/s')"; done; python bench.py --steps 80 --warmup 5 --force-sharded --emulate-world 8 --no-cpu-baseline --no-parity --no-alt-arith --no-profile 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('emulated world 8 (80 steps):', round(d['value'],1), 'frames/s')"
  for g in 2 4 8; do python bench.py --steps 40 --warmup 8 --force-sharded --emulate-world $g --window 1 --no-cpu-baseline --no-parity --no-alt-arith --no-profile 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('per-frame mode (--window 1), emulated world $g:', round(d['value'],1), 'frames/s')"; done) > $OUT/emulated_world.txt
 IO_ALL=1 timeout 300 python tools/io_paths3.py 2>&1 | grep -v amdgpu.ids > $OUT/io_paths.txt; IO_ALL=1 IO_THREADS=1 timeout 300 python tools/io_paths3.py 2>&1 | grep -v amdgpu.ids >> $OUT/io_paths.txt
