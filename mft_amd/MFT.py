@@ -86,6 +86,7 @@ class MFT():
         assert time_direction in [+1, -1]
         self.time_direction = time_direction
         self.flow_cache = flow_cache
+        self._reset_guard_state()
         if hasattr(self.flower, "reset_cache"):
             self.flower.reset_cache()
         if hasattr(self.flower, "set_nominal_pairs"):      # kernel choices are made for the steady-state batch, not per call
@@ -108,6 +109,23 @@ class MFT():
         meta = SimpleNamespace()
         meta.result = self.memory[self.start_frame_i]['result'].clone().cpu()
         return meta
+
+    def _reset_guard_state(self):
+        """init() on a used tracker starts clean: nothing of the previous sequence's non-finite guard may raise in the new one.  The
+        plugin's device-side counters are cumulative and the lazy host path reads snapshots of them, so a poisoned frame of the old
+        sequence would otherwise fail the first access of every later result.  Waits for the pinned result copies still in flight
+        (their buffers must not be recycled under them), drops the pending counter snapshot and the frame count of the periodic
+        check, and zeroes the counters (one small read per engine: init() synchronises anyway when it returns the CPU identity).
+        The counters belong to the flow plugin: trackers that share one share them, and this clears them for all."""
+        for ev, _, _ in getattr(self, "_pending_host", None) or ():
+            ev.synchronize()
+        self._pending_host = []
+        self._nf_ring = []
+        self._frames_unchecked = 0
+        if hasattr(self.flower, "nonfinite_count"):
+            stale = self.flower.nonfinite_count(reset=True)
+            if stale:
+                logger.warning("init(): %d non-finite output pixels counted by the flow plugin before this sequence were cleared", stale)
 
     # ----------------------------------------------------------------- track
     def _plan(self, frame_i=None):
@@ -207,13 +225,15 @@ class MFT():
         return v if isinstance(v, bool) else True
 
     def _host_result_async(self, result):
-        """The frame's result -> one pinned host buffer [4, H, W] by the copy kernel, on the caller's stream right behind the selection
+        """The frame's result -> one pinned host buffer by the copy kernel, on the caller's stream right behind the selection
         kernel (no SDMA queue: mft_amd/video.py ResultDrain found a pinned download there holding back the pinned uploads
-        queued behind it).  The buffer comes from torch's caching pinned allocator: results the caller drops are recycled, results it
+        queued behind it).  The buffer is flat and every plane starts on a 16-byte boundary in it (PendingHostResult.plane_offsets):
+        the copy kernel moves 16 bytes per lane, and H * W need not be a multiple of 4.  It comes from torch's caching pinned
+        allocator: results the caller drops are recycled, results it
         keeps stay pinned (4.2 MB each at 512 x 512).  The tracker holds on to every buffer until its copy has run, so that a
         result dropped unread cannot be recycled -- by this or any other user of the pinned pool -- under the copy that fills it."""
-        host = torch.empty((4, self.img_H, self.img_W), dtype=torch.float32, pin_memory=True)
-        for dst, src in ((host[0:2], result.flow), (host[2:3], result.occlusion), (host[3:4], result.sigma)):
+        host = PendingHostResult.host_buffer(self.img_H, self.img_W)
+        for dst, src in zip(PendingHostResult.plane_views(host, self.img_H, self.img_W), result.planes()):
             ops.copy_bytes(src.contiguous(), dst)
         check = words = None
         every = self.C.nonfinite_check_every
@@ -238,7 +258,7 @@ class MFT():
         pending.append((ev, host, words))
         while len(pending) > 64:                  # (a caller that never reads: bound the list, the oldest copy ran long ago)
             pending.pop(0)[0].synchronize()
-        return PendingHostResult(host, ev, on_wait=check)
+        return PendingHostResult(host, ev, on_wait=check, shape=(self.img_H, self.img_W))
 
     def _check_nonfinite(self, synced):
         """The flow plugin counts, on the device, output pixels the reference could not have produced from finite activations: a

@@ -35,7 +35,9 @@ def copy_bytes(src: torch.Tensor, dst: torch.Tensor):
         raise MftxError("copy_bytes: tensors must be on the device or in pinned host memory")
     if not (src.is_contiguous() and dst.is_contiguous()) or src.numel() * src.element_size() != dst.numel() * dst.element_size():
         raise MftxError("copy_bytes: contiguous tensors of the same size in bytes")
-    check(_lib.load().mftx_copy_bytes(src.data_ptr(), dst.data_ptr(), src.numel() * src.element_size(), _stream()), "mftx_copy_bytes")
+    nbytes = src.numel() * src.element_size()
+    if nbytes:                                    # (an empty tensor has no storage: its data_ptr() is null, which the library refuses)
+        check(_lib.load().mftx_copy_bytes(src.data_ptr(), dst.data_ptr(), nbytes, _stream()), "mftx_copy_bytes")
     return dst
 
 

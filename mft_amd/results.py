@@ -211,9 +211,11 @@ class PendingHostResult(FlowOUTrackingResult):
     """A ``FlowOUTrackingResult`` on the HOST whose planes are still on their way: what ``MFT.track()`` returns as ``meta.result``
     (MFT/MFT.py:145-148 returns a CPU result from every call) without making every call wait for the GPU.
 
-    The three planes are views of one pinned host buffer ``[4, H, W]`` that a copy kernel, enqueued behind the frame's selection
-    kernel, fills; the first access to ``flow`` / ``occlusion`` / ``sigma`` (or any method, ``clone``, ``cpu``, pickling) waits
-    for the event behind that copy -- once -- and from then on this is an ordinary CPU result.  A caller that reads every result
+    The three planes are views of one flat pinned host buffer that a copy kernel, enqueued behind the frame's selection kernel, fills
+    (``host_buffer`` / ``plane_offsets``: every plane starts on a 16-byte boundary whatever H x W is -- the copy kernel moves 16 bytes
+    per lane -- so at frame sizes with H * W % 4 != 0 there are a few unused floats between the planes); the first access to ``flow`` /
+    ``occlusion`` / ``sigma`` (or any method, ``clone``, ``cpu``, pickling) waits for the event behind that copy -- once -- and from
+    then on this is an ordinary CPU result.  A caller that reads every result
     right away (the reference's demo.py:59-65) synchronises per frame exactly as with the reference; a caller that collects
     results and reads them later (a runner that writes its outputs at the end, a consumer thread) lets the tracker run ahead and
     gets the pipelined rate.  ``ready()`` asks without waiting.
@@ -221,11 +223,39 @@ class PendingHostResult(FlowOUTrackingResult):
     The non-finite guard of the flow plugin rides along: a 16-byte snapshot of every engine's counter lands in pinned words
     behind the planes, and the first access raises ``FloatingPointError`` if any is set (``on_wait``)."""
 
-    def __init__(self, host, event, on_wait=None):
-        assert host.dim() == 3 and host.shape[0] == 4 and not host.is_cuda
-        self.H, self.W = host.shape[1:]
+    @staticmethod
+    def plane_offsets(H, W):
+        """((flow, occlusion, sigma) offsets, total length) in floats of the flat host buffer: each offset a multiple of 4 floats."""
+        n = H * W
+        o_occl = -(-2 * n // 4) * 4
+        o_sigma = o_occl + -(-n // 4) * 4
+        return (0, o_occl, o_sigma), o_sigma + n
+
+    @classmethod
+    def host_buffer(cls, H, W):
+        """An uninitialised pinned buffer for one H x W result (torch's caching pinned allocator: dropped results are recycled)."""
+        return torch.empty(cls.plane_offsets(H, W)[1], dtype=torch.float32, pin_memory=True)
+
+    @classmethod
+    def plane_views(cls, host, H, W):
+        """The (flow [2,H,W], occlusion [1,H,W], sigma [1,H,W]) views of a ``host_buffer(H, W)``."""
+        (o_flow, o_occl, o_sigma), total = cls.plane_offsets(H, W)
+        assert host.dim() == 1 and host.numel() == total and host.dtype == torch.float32
+        n = H * W
+        return host[o_flow:o_flow + 2 * n].view(2, H, W), host[o_occl:o_occl + n].view(1, H, W), host[o_sigma:o_sigma + n].view(1, H, W)
+
+    def __init__(self, host, event, on_wait=None, shape=None):
+        """host: the flat buffer of ``host_buffer(H, W)`` with ``shape = (H, W)``, or (shape None) one contiguous [4, H, W] tensor."""
+        assert not host.is_cuda
+        if shape is None:
+            assert host.dim() == 3 and host.shape[0] == 4
+            self.H, self.W = host.shape[1:]
+            planes = host[0:2], host[2:3], host[3:4]
+        else:
+            self.H, self.W = int(shape[0]), int(shape[1])
+            planes = self.plane_views(host, self.H, self.W)
         self._host, self._event, self._on_wait = host, event, on_wait
-        self._flow, self._occlusion, self._sigma = host[0:2], host[2:3], host[3:4]
+        self._flow, self._occlusion, self._sigma = planes
 
     def ready(self):
         """True once the planes have arrived (never waits)."""

@@ -16,6 +16,7 @@ imports ``/root/reference`` read-only) and committed under ``tests/golden/``;
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from types import SimpleNamespace
 
@@ -23,7 +24,30 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-F32 = torch.float32
+F32 = torch.float32        # the working precision: float32 like the reference, float64 inside ``precision(torch.float64)``
+
+
+@contextlib.contextmanager
+def precision(dtype):
+    """Run the oracle in another floating-point type: ``with precision(torch.float64): ...`` evaluates the same formulas (the
+    float32-rounded constants of the reference included) in fp64, with weights from ``cast_weights``.  The difference between the
+    fp32 and the fp64 oracle is the reference's own rounding noise -- the yardstick tests measure a HIP result against.  Sets this
+    module's working type and torch's default dtype (tensors the oracle creates without naming one) and restores both; not
+    re-entrant across threads."""
+    global F32
+    saved = (F32, torch.get_default_dtype())
+    F32 = dtype
+    torch.set_default_dtype(dtype)
+    try:
+        yield
+    finally:
+        F32 = saved[0]
+        torch.set_default_dtype(saved[1])
+
+
+def cast_weights(sd, dtype):
+    """The state dict with every floating-point tensor in ``dtype`` (integer buffers such as num_batches_tracked stay)."""
+    return {k: (v.to(dtype) if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in sd.items()}
 
 
 # ---------------------------------------------------------------------------
