@@ -445,6 +445,33 @@ int mftx_chain_select_packed(int K,
                              float thr, int H, int W,
                              float *flowO, float *occlO, float *sigmaO, int8_t *chosen, void *stream);
 
+/* The same for T templates of one video in ONE launch (mft_amd/multi.py): template j chains and selects among its own
+ * K[j] candidates (1 .. MFTX_MAX_CANDIDATES) and writes its own outputs flowO[j] / occlO[j] / sigmaO[j] / chosen[j]
+ * (chosen, or any chosen[j], may be NULL).  flowL / occlL / sigmaL / packedR are HOST arrays of K[0] + ... + K[T-1]
+ * device pointers, template after template; a right operand may appear under many templates (it then comes from HBM
+ * once and from the caches afterwards).  One threshold and one H x W per call.  The descriptors travel in the kernel
+ * arguments, so T templates go out as ceil(T / 12) launches (ceil(T / 6) if a K[j] exceeds 8) on `stream`: no
+ * allocation, no copy, no synchronisation.  Template j's output is bitwise that of mftx_chain_select_packed called with
+ * its candidates alone. */
+int mftx_chain_select_multi(int T, const int *K,
+                            const float *const *flowL, const float *const *occlL, const float *const *sigmaL,
+                            const float *const *packedR,
+                            float thr, int H, int W,
+                            float *const *flowO, float *const *occlO, float *const *sigmaO, int8_t *const *chosen,
+                            void *stream);
+
+/* Point read-out of T results in one launch (MFT/point_tracking.py:6-27: warp_forward_points + sample).  flow / occl /
+ * sigma: HOST arrays of T device pointers ([2][H][W], [1][H][W], [1][H][W]).  tmpl [N] int32, xy [N][2] float32 (device):
+ * point i lies at xy[i] on template tmpl[i]; that template's planes are sampled there bilinearly (zeros outside,
+ * align_corners=True, the reference's normalise / un-normalise round trip: the chain's sampler) and
+ * (x + flow x, y + flow y, occlusion, sigma) is written as one 16-byte store to table[i * row_stride + 4 * column]
+ * (device, float32, 16-byte aligned; row_stride in floats, a multiple of 4: a table laid out [N][frames][4] has
+ * row_stride = 4 * frames and column = the frame).  Points whose tmpl[i] is outside 0 .. T-1 are left alone.  More than
+ * 128 templates go out as several launches. */
+int mftx_sample_points(int T, const float *const *flow, const float *const *occl, const float *const *sigma,
+                       int H, int W, int N, const int *tmpl, const float *xy,
+                       float *table, long long row_stride, int column, void *stream);
+
 /* ---- 8f-2: flow-cache codec (".flowouX16" entries) -----------------------------
  * Replaces compress_channel / decompress_channel of write_flowou_X16 / read_flowou_X16
  * (MFT/utils/io.py:495-512, 548-551): per-channel min/max, uint16 quantisation with

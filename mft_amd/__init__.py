@@ -46,6 +46,9 @@ def __getattr__(name):  # lazy: these import torch-heavy modules
         _m = importlib.import_module(__name__ + ".MFT")       # (`from . import MFT` would ask this very function for "MFT": recursion)
         globals()["MFT"] = _m.MFT                             # the CLASS, as the docstring promises (importing the submodule bound its own name here)
         return getattr(_m, name)
+    if name == "MultiTemplateMFT":
+        from .multi import MultiTemplateMFT
+        return MultiTemplateMFT
     if name == "RAFTWrapper":
         from .raft import RAFTWrapper
         return RAFTWrapper

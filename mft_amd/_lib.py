@@ -110,6 +110,10 @@ SIGNATURES = {
     "mftx_select": (C.c_int, [C.c_int, _PP, _PP, _PP, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 5),
     "mftx_chain_select": (C.c_int, [C.c_int] + [_PP] * 6 + [C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 5),
     "mftx_chain_select_packed": (C.c_int, [C.c_int] + [_PP] * 4 + [C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    "mftx_chain_select_multi": (C.c_int, [C.c_int, C.POINTER(C.c_int)] + [_PP] * 4 + [C.c_float, C.c_int, C.c_int] + [_PP] * 4
+                                + [C.c_void_p]),
+    "mftx_sample_points": (C.c_int, [C.c_int, _PP, _PP, _PP, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
     "mftx_quantize_workspace_bytes": (C.c_size_t, []),
     "mftx_quantize_u16": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mftx_dequantize_u16": (C.c_int, [C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),

@@ -307,6 +307,117 @@ __global__ __launch_bounds__(256) void select4_kernel(SelSet ss, float thr, int 
     write_selected4(b, H, W, x, y, flowO, occlO, sigmaO, chosen);
 }
 
+// ---- MANY TEMPLATES of one video in one launch (mft_amd/multi.py): template j = blockIdx.z chains its own K[j] candidates
+// and selects among them.  Per pixel the arithmetic is chain_select_packed_kernel's, operation for operation -- the output of
+// template j is bitwise what mftx_chain_select_packed gives for that template's candidates alone -- and so is the latency
+// structure: all left planes first, then the taps in batches of four candidates.  K is a run-time value below the
+// compile-time bound KMAX, uniform per block (no divergence).  The descriptors travel by value in the kernel arguments (they
+// are read with scalar loads, indexed by blockIdx.z); a launch's argument block is limited to 4 KB, hence TN templates per
+// launch.  The right operands the templates share (the finite-delta pairs of a frame) are read once from HBM and then
+// from L2 / Infinity Cache by the other templates' blocks.
+template <int KMAX>
+struct MultiTmpl {
+    int K;
+    Planes L[KMAX];
+    const float4 *R[KMAX];
+    float *flowO, *occlO, *sigmaO;
+    int8_t *chosen;
+};
+constexpr int MULTI_TN8 = 12;      // 12 x 296 B = 3552 B
+constexpr int MULTI_TN16 = 6;      //  6 x 552 B = 3312 B
+template <int KMAX, int TN>
+struct MultiSet { MultiTmpl<KMAX> t[TN]; };
+static_assert(sizeof(MultiSet<8, MULTI_TN8>) + 32 <= 4096 && sizeof(MultiSet<MFTX_MAX_CANDIDATES, MULTI_TN16>) + 32 <= 4096,
+              "kernel arguments of chain_select_multi_kernel exceed 4 KB");
+
+template <int KMAX, int TN>     // KMAX = 8: batched taps; KMAX = 16: any K, candidate by candidate (as chain_select_packed_kernel<0>)
+__global__ __launch_bounds__(256) void chain_select_multi_kernel(MultiSet<KMAX, TN> ms, float thr, int H, int W, float sx,
+                                                                 float sy) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y;
+    if (x >= W) return;
+    const MultiTmpl<KMAX> &t = ms.t[blockIdx.z];
+    const int K = t.K;
+    const long long pix = (long long)y * W + x, plane = (long long)H * W;
+    Best b;
+    b.score = 0.f; b.k = 0; b.c = Chained{0.f, 0.f, 0.f, 0.f};
+    if constexpr (KMAX > 8) {
+        for (int k = 0; k < K; ++k) {
+            const Planes L = t.L[k];
+            const ChainPrep c = chain_prep(L.flow[pix], L.flow[plane + pix], H, W, x, y, sx, sy);
+            const float4 *R = t.R[k];
+            consider(b, chain_finish(c, L.occl[pix], L.sigma[pix], packed_tap(R, H, W, c.y0, c.x0), packed_tap(R, H, W, c.y0, c.x0 + 1),
+                                     packed_tap(R, H, W, c.y0 + 1, c.x0), packed_tap(R, H, W, c.y0 + 1, c.x0 + 1)), k, thr);
+        }
+    } else {
+        float lfx[KMAX], lfy[KMAX], loc[KMAX], lsg[KMAX];
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) {
+            if (k < K) {
+                lfx[k] = t.L[k].flow[pix]; lfy[k] = t.L[k].flow[plane + pix];
+                loc[k] = t.L[k].occl[pix]; lsg[k] = t.L[k].sigma[pix];
+            }
+        }
+#pragma unroll
+        for (int k0 = 0; k0 < KMAX; k0 += 4) {
+            constexpr int B = 4;
+            ChainPrep c[B];
+            float4 tp[B][4];
+#pragma unroll
+            for (int j = 0; j < B; ++j) {
+                if (k0 + j < K) {
+                    c[j] = chain_prep(lfx[k0 + j], lfy[k0 + j], H, W, x, y, sx, sy);
+                    const float4 *R = t.R[k0 + j];
+                    tp[j][0] = packed_tap(R, H, W, c[j].y0, c[j].x0);
+                    tp[j][1] = packed_tap(R, H, W, c[j].y0, c[j].x0 + 1);
+                    tp[j][2] = packed_tap(R, H, W, c[j].y0 + 1, c[j].x0);
+                    tp[j][3] = packed_tap(R, H, W, c[j].y0 + 1, c[j].x0 + 1);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < B; ++j)
+                if (k0 + j < K)
+                    consider(b, chain_finish(c[j], loc[k0 + j], lsg[k0 + j], tp[j][0], tp[j][1], tp[j][2], tp[j][3]), k0 + j, thr);
+        }
+    }
+    write_selected(b, H, W, x, y, t.flowO, t.occlO, t.sigmaO, t.chosen);
+}
+
+// ---- point read-out of many templates' results in one launch (MFT/point_tracking.py:6-27: warp_forward_points + sample).
+// Point i belongs to template tmpl[i] and sits at (xy[2 i], xy[2 i + 1]) on that template's frame: its flow / occlusion /
+// sigma planes are sampled there with chain_px's sampler (bilinear, zeros outside, align_corners=True, after the
+// normalise / un-normalise round trip) and (x + fx, y + fy, occlusion, sigma) goes, as ONE 16-byte store, to row i, column
+// `column` of the caller's table.  One thread per point; a launch carries the planes of up to SAMPLE_TN templates in its
+// arguments and leaves the points of other templates alone.
+constexpr int SAMPLE_TN = 128;     // 128 x 24 B = 3072 B
+struct SampleSet { Planes t[SAMPLE_TN]; };
+static_assert(sizeof(SampleSet) + 64 <= 4096, "kernel arguments of sample_points_kernel exceed 4 KB");
+
+__global__ __launch_bounds__(256) void sample_points_kernel(SampleSet ss, int t0, int nt, int H, int W, float sx, float sy,
+                                                            int N, const int *__restrict__ tmpl, const float *__restrict__ xy,
+                                                            float *__restrict__ table, long long row_stride, int column) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const int j = tmpl[i] - t0;
+    if (j < 0 || j >= nt) return;
+    const Planes P = ss.t[j];
+    const long long plane = (long long)H * W;
+    const float px = xy[2 * (long long)i], py = xy[2 * (long long)i + 1];
+    const float ix = ((px * sx - 1.f) + 1.f) / 2.f * (float)(W - 1);
+    const float iy = ((py * sy - 1.f) + 1.f) / 2.f * (float)(H - 1);
+    const float flx = floorf(ix), fly = floorf(iy);
+    const float wx = ix - flx, wy = iy - fly;
+    const int x0 = (int)fminf(fmaxf(flx, -1.0e6f), 1.0e6f);
+    const int y0 = (int)fminf(fmaxf(fly, -1.0e6f), 1.0e6f);
+    const float w00 = (1.f - wx) * (1.f - wy), w01 = wx * (1.f - wy), w10 = (1.f - wx) * wy, w11 = wx * wy;
+    auto samp = [&](const float *pl) {
+        return tap(pl, H, W, y0, x0) * w00 + tap(pl, H, W, y0, x0 + 1) * w01 +
+               tap(pl, H, W, y0 + 1, x0) * w10 + tap(pl, H, W, y0 + 1, x0 + 1) * w11;
+    };
+    const float4 o = make_float4(px + samp(P.flow), py + samp(P.flow + plane), samp(P.occl), samp(P.sigma));
+    *reinterpret_cast<float4 *>(table + (long long)i * row_stride + 4 * (long long)column) = o;
+}
+
 }  // namespace mftx
 
 using namespace mftx;
@@ -435,4 +546,106 @@ extern "C" int mftx_chain_select_packed(int K, const float *const *flowL, const 
     }
 #undef CSP_LAUNCH
     return check_launch("chain_select_packed");
+}
+
+template <int KMAX, int TN>
+static void launch_multi(int n, const int *K, const float *const *flowL, const float *const *occlL,
+                         const float *const *sigmaL, const float *const *packedR, float thr, int H, int W, float sx,
+                         float sy, float *const *flowO, float *const *occlO, float *const *sigmaO, int8_t *const *chosen,
+                         hipStream_t stream) {
+    MultiSet<KMAX, TN> ms = {};
+    for (int j = 0, c = 0; j < n; ++j) {
+        MultiTmpl<KMAX> &t = ms.t[j];
+        t.K = K[j];
+        for (int k = 0; k < K[j]; ++k, ++c) {
+            t.L[k] = Planes{flowL[c], occlL[c], sigmaL[c]};
+            t.R[k] = reinterpret_cast<const float4 *>(packedR[c]);
+        }
+        t.flowO = flowO[j]; t.occlO = occlO[j]; t.sigmaO = sigmaO[j];
+        t.chosen = chosen ? chosen[j] : nullptr;
+    }
+    hipLaunchKernelGGL((chain_select_multi_kernel<KMAX, TN>), dim3(cdiv(W, 256), H, n), dim3(256), 0, stream, ms, thr, H, W,
+                       sx, sy);
+}
+
+extern "C" int mftx_chain_select_multi(int T, const int *K, const float *const *flowL, const float *const *occlL,
+                                       const float *const *sigmaL, const float *const *packedR, float thr, int H, int W,
+                                       float *const *flowO, float *const *occlO, float *const *sigmaO,
+                                       int8_t *const *chosen, void *stream) {
+    if (T < 1) return fail(MFTX_E_ARG, "chain_select_multi: T must be >= 1");
+    if (!K || !flowL || !occlL || !sigmaL || !packedR || !flowO || !occlO || !sigmaO)
+        return fail(MFTX_E_ARG, "chain_select_multi: null pointer");
+    if (H < 2 || W < 2) return fail(MFTX_E_ARG, "chain_select_multi: H and W must be >= 2");
+    int maxK = 0;
+    long long total = 0;
+    for (int j = 0; j < T; ++j) {
+        if (K[j] < 1 || K[j] > MFTX_MAX_CANDIDATES)
+            return fail(MFTX_E_ARG, "chain_select_multi: K[%d] must be in 1..%d", j, MFTX_MAX_CANDIDATES);
+        if (!flowO[j] || !occlO[j] || !sigmaO[j]) return fail(MFTX_E_ARG, "chain_select_multi: null output of template %d", j);
+        for (int k = 0; k < K[j]; ++k, ++total) {
+            if (!flowL[total] || !occlL[total] || !sigmaL[total] || !packedR[total])
+                return fail(MFTX_E_ARG, "chain_select_multi: null candidate %d of template %d", k, j);
+            if (!aligned16(packedR[total]))
+                return fail(MFTX_E_ALIGN, "chain_select_multi: packed operands must be 16-byte aligned");
+        }
+        maxK = K[j] > maxK ? K[j] : maxK;
+    }
+    float sx, sy;
+    scales(H, W, sx, sy);
+    // bytes per pixel: every left operand (16) and every output (16) once, every DISTINCT right operand (16) once
+    double bytes = 0.0;
+    if (prof_enabled()) {
+        long long distinct = 0;
+        for (long long c = 0; c < total; ++c) {
+            bool seen = false;
+            for (long long d = 0; d < c && !seen; ++d) seen = packedR[d] == packedR[c];
+            distinct += !seen;
+        }
+        bytes = (16.0 * total + 16.0 * distinct + 16.0 * T) * H * W;
+    }
+    ProfScope prof(PC_CHAIN, (hipStream_t)stream, bytes);
+    const int per = maxK <= 8 ? MULTI_TN8 : MULTI_TN16;
+    for (int j0 = 0, c0 = 0; j0 < T; j0 += per) {
+        const int n = T - j0 < per ? T - j0 : per;
+        if (maxK <= 8)
+            launch_multi<8, MULTI_TN8>(n, K + j0, flowL + c0, occlL + c0, sigmaL + c0, packedR + c0, thr, H, W, sx, sy,
+                                       flowO + j0, occlO + j0, sigmaO + j0, chosen ? chosen + j0 : nullptr, (hipStream_t)stream);
+        else
+            launch_multi<MFTX_MAX_CANDIDATES, MULTI_TN16>(n, K + j0, flowL + c0, occlL + c0, sigmaL + c0, packedR + c0, thr, H,
+                                                          W, sx, sy, flowO + j0, occlO + j0, sigmaO + j0,
+                                                          chosen ? chosen + j0 : nullptr, (hipStream_t)stream);
+        for (int j = j0; j < j0 + n; ++j) c0 += K[j];
+        const int rc = check_launch("chain_select_multi");
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+extern "C" int mftx_sample_points(int T, const float *const *flow, const float *const *occl, const float *const *sigma,
+                                  int H, int W, int N, const int *tmpl, const float *xy, float *table,
+                                  long long row_stride, int column, void *stream) {
+    if (T < 1 || N < 0) return fail(MFTX_E_ARG, "sample_points: need T >= 1, N >= 0");
+    if (!flow || !occl || !sigma) return fail(MFTX_E_ARG, "sample_points: null pointer");
+    if (H < 2 || W < 2) return fail(MFTX_E_ARG, "sample_points: H and W must be >= 2");
+    for (int j = 0; j < T; ++j)
+        if (!flow[j] || !occl[j] || !sigma[j]) return fail(MFTX_E_ARG, "sample_points: null planes of template %d", j);
+    if (N == 0) return 0;
+    if (!tmpl || !xy || !table) return fail(MFTX_E_ARG, "sample_points: null pointer");
+    if (column < 0 || row_stride < 4 * ((long long)column + 1) || row_stride % 4)
+        return fail(MFTX_E_ARG, "sample_points: row_stride must be a multiple of 4 floats that holds column %d", column);
+    if (!aligned16(table)) return fail(MFTX_E_ALIGN, "sample_points: the table must be 16-byte aligned");
+    float sx, sy;
+    scales(H, W, sx, sy);
+    // per point: template index + xy (12 B), 4 taps of 4 planes (64 B), one table entry (16 B)
+    ProfScope prof(PC_CHAIN, (hipStream_t)stream, (12.0 + 64.0 + 16.0) * N);
+    for (int t0 = 0; t0 < T; t0 += SAMPLE_TN) {
+        const int nt = T - t0 < SAMPLE_TN ? T - t0 : SAMPLE_TN;
+        SampleSet ss = {};
+        for (int j = 0; j < nt; ++j) ss.t[j] = Planes{flow[t0 + j], occl[t0 + j], sigma[t0 + j]};
+        hipLaunchKernelGGL(sample_points_kernel, dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, ss, t0, nt, H, W, sx,
+                           sy, N, tmpl, xy, table, row_stride, column);
+        const int rc = check_launch("sample_points");
+        if (rc) return rc;
+    }
+    return 0;
 }

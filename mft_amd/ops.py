@@ -679,6 +679,70 @@ def chain_select_packed(Ls, Rs, thr, want_chosen=False):
     return out + (chosen,)
 
 
+def chain_select_multi(templates, thr, want_chosen=False):
+    """``chain_select_packed`` for many templates in one launch (``mftx_chain_select_multi``): templates = T x (Ls, Rs) with
+    Ls = K_j x (flow[2,H,W], occl[1,H,W], sigma[1,H,W]) and Rs = K_j x [H,W,4]; the same right operand may appear under
+    several templates.  -> T x (flow, occl, sigma, chosen | None), each bitwise what ``chain_select_packed(Ls, Rs, thr)`` gives."""
+    lib = _lib.load()
+    templates = list(templates)
+    if not templates:
+        return []
+    _, H, W = templates[0][0][0][0].shape
+    Ks, cols, rs = [], [], []
+    for Ls, Rs in templates:
+        if len(Ls) != len(Rs) or not 1 <= len(Ls) <= _lib.MAX_CANDIDATES:
+            raise MftxError(f"chain_select_multi: every template needs 1..{_lib.MAX_CANDIDATES} (left, right) pairs")
+        Ks.append(len(Ls))
+        cols += [_planes(c, H, W) for c in Ls]
+        for r in Rs:
+            if tuple(r.shape) != (H, W, 4):
+                raise MftxError("packed FlowOU must be [H, W, 4]")
+            rs.append(_chk(r, "packed"))
+    T = len(templates)
+    dev = templates[0][0][0][0].device
+    # one allocation per plane kind for all templates (the outputs are views of it)
+    flow = torch.empty(T, 2, H, W, dtype=torch.float32, device=dev)
+    occl = torch.empty(T, 1, H, W, dtype=torch.float32, device=dev)
+    sigma = torch.empty(T, 1, H, W, dtype=torch.float32, device=dev)
+    chosen = torch.empty(T, H, W, dtype=torch.int8, device=dev) if want_chosen else None
+    larrs = [_lib.ptr_array(list(c)) for c in zip(*cols)] + [_lib.ptr_array(rs)]
+    oarrs = [_lib.ptr_array([t[j].data_ptr() for j in range(T)]) for t in (flow, occl, sigma)]
+    carr = _lib.ptr_array([chosen[j].data_ptr() for j in range(T)]) if want_chosen else (None, None)
+    check(lib.mftx_chain_select_multi(T, (C.c_int * T)(*Ks), *[a[0] for a in larrs], float(thr), H, W,
+                                      *[a[0] for a in oarrs], carr[0], _stream()), "mftx_chain_select_multi")
+    return [(flow[j], occl[j], sigma[j], chosen[j] if want_chosen else None) for j in range(T)]
+
+
+def sample_points(results, tmpl, xy, table, column):
+    """Point read-out of many results in one launch (``mftx_sample_points``): results = T x (flow[2,H,W], occl[1,H,W],
+    sigma[1,H,W]); tmpl [N] int32 and xy [N,2] float32 on the device -- point i lies at xy[i] on results[tmpl[i]]; table: a
+    float32 device tensor [N, frames, 4] (or [N, 4]) the caller owns.  Row i, column ``column`` of it receives
+    (x + flow x, y + flow y, occlusion, sigma) -- ``warp_forward_points`` and ``sample`` of the reference's results API;
+    nothing else of the table is touched.  Returns ``table``."""
+    lib = _lib.load()
+    results = list(results)
+    N = int(tmpl.shape[0])
+    if not results or N == 0:
+        return table
+    _, H, W = results[0][0].shape
+    cols = list(zip(*[_planes(r, H, W) for r in results]))
+    arrs = [_lib.ptr_array(list(c)) for c in cols]
+    if tuple(xy.shape) != (N, 2) or tmpl.dim() != 1:
+        raise MftxError("sample_points: tmpl must be [N], xy [N, 2]")
+    if table.dim() == 2:
+        frames = 1
+    elif table.dim() == 3:
+        frames = int(table.shape[1])
+    else:
+        raise MftxError("sample_points: the table must be [N, frames, 4] or [N, 4]")
+    if int(table.shape[0]) != N or int(table.shape[-1]) != 4 or not 0 <= int(column) < frames:
+        raise MftxError("sample_points: the table must be [N, frames, 4] with 0 <= column < frames")
+    check(lib.mftx_sample_points(len(results), arrs[0][0], arrs[1][0], arrs[2][0], H, W, N, _chk(tmpl, "tmpl", torch.int32),
+                                 _chk(xy, "xy"), _chk(table, "table"), 4 * frames, int(column), _stream()),
+          "mftx_sample_points")
+    return table
+
+
 _quant_ws = {}
 
 

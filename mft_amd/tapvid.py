@@ -314,6 +314,47 @@ def run_sequence(tracker, video, query_points, query_mode, flow_cache=None, devi
     return {"tracks": pred_tracks[None], "occluded": pred_occluded[None]}
 
 
+def run_sequence_multi(tracker, video, query_points, query_mode, device=None, on_result=None, max_templates=None):
+    """``run_sequence`` in lockstep passes (``mft_amd/multi.py``): ``tracker`` is a ``MultiTemplateMFT``; all distinct start
+    frames are tracked in ONE forward pass over the video and, for 'strided', one backward pass -- in groups of
+    ``max_templates`` (default: the tracker's) -- instead of one complete tracker run per start frame and direction.  Same
+    arguments and the same return value as ``run_sequence``: {'tracks': (1, n, T, 2) xy on the 256 x 256 raster, 'occluded':
+    (1, n, T) occlusion scores}; the points are read out on the device and downloaded once per pass.
+    ``on_result(start_frame, direction, frame_i, result)``: called for every template and frame with the dense result (on
+    the device; exports)."""
+    if query_mode not in ("first", "strided"):
+        raise ValueError("Unknown query mode " + query_mode)
+    query_points = np.asarray(query_points).astype(np.int64)
+    n_frames, H, W = len(video), video[0].shape[0], video[0].shape[1]
+    n_q = query_points.shape[0]
+    pred_tracks = np.zeros((n_q, n_frames, 2))
+    pred_occluded = np.zeros((n_q, n_frames))
+    group = min(int(max_templates), tracker.max_templates) if max_templates else tracker.max_templates
+    if group < 1:
+        raise ValueError("max_templates must be at least 1")
+    starts = [int(s) for s in np.unique(query_points[:, 0])]
+    sels = {s: query_points[:, 0] == s for s in starts}
+    queries = {s: query_points[sels[s], 1:][:, ::-1].astype(np.float32) for s in starts}
+    directions = (("forward", +1), ("backward", -1)) if query_mode == "strided" else (("forward", +1),)
+    for direction, step in directions:
+        ordered = starts if step > 0 else starts[::-1]
+        for g0 in range(0, len(ordered), group):
+            part = ordered[g0: g0 + group]
+            tracker.init(part, time_direction=step, queries={s: queries[s] for s in part}, n_frames=n_frames)
+            for frame_i in (range(part[0], n_frames) if step > 0 else range(part[0], -1, -1)):
+                metas = tracker.track(frame_i, video[frame_i])
+                if on_result is not None:
+                    for s, meta in metas.items():
+                        on_result(s, direction, frame_i, meta.result)
+            for s, (coords, occl) in tracker.point_tracks().items():
+                visited = slice(s, n_frames) if step > 0 else slice(0, s + 1)
+                rows = np.flatnonzero(sels[s])
+                pred_tracks[rows, visited] = coords[:, visited]
+                pred_occluded[rows, visited] = occl[:, visited]
+    pred_tracks *= np.array([256.0 / W, 256.0 / H])
+    return {"tracks": pred_tracks[None], "occluded": pred_occluded[None]}
+
+
 def _query_modes(mode):
     if mode not in ("first", "strided", "both"):
         raise ValueError("Unknown query mode " + str(mode))
@@ -332,7 +373,8 @@ def result_path(export, tracker_name, sequence_name, query_mode):
 
 
 def run_dataset(dataset_conf, configs, export, cache_root, mode="both", cont=False, seqs=None, write_flow=False,
-                ram_cache_limit=30, gpu_cache_limit=5, tracker=None, device="cuda", debug=False, cache_factory=None):
+                ram_cache_limit=30, gpu_cache_limit=5, tracker=None, device="cuda", debug=False, cache_factory=None,
+                multi_template=False):
     """The TAP-Vid run of ``MFT/runners/run_MFT_tapvid.py:85-247``: every sequence of every pickle of ``dataset_conf``
     (``.pickles``, ``.scaling``, ``.name``) is tracked for every query mode and tracker config, all runs of a sequence
     sharing one flow cache (``cache_root/<dataset>/<flow name>/<sequence>``, emptied before and removed after), and the
@@ -340,10 +382,16 @@ def run_dataset(dataset_conf, configs, export, cache_root, mode="both", cont=Fal
     256 x 256 raster, 'occluded' (1, n, T) scores}.  ``cont``: existing result files are skipped.  ``write_flow``: the
     frame-0 template's results of the 'first' run are written as ``flowous/<sequence>/0--<i>.flowouX16.pkl``.
     ``cache_factory(dir, max_RAM_MB, max_GPU_RAM_MB)`` defaults to ``mft_amd.io.FlowCache`` (HBM tier first: on an MI355X
-    ``gpu_cache_limit`` can be raised to hundreds of GB).  -> list of {'sequence', 'mode', 'tracker', 'path', 'skipped'}."""
+    ``gpu_cache_limit`` can be raised to hundreds of GB).  -> list of {'sequence', 'mode', 'tracker', 'path', 'skipped'}.
+    ``multi_template``: all start frames of a sequence and direction are tracked in one lockstep pass
+    (``run_sequence_multi``; ``tracker``, if given, is a ``MultiTemplateMFT``); no flow cache is created -- within a pass
+    no pair is computed twice -- and the same files are written."""
     from .io import FlowCache
     configs = list(configs)
     validate_configs(configs)
+    if tracker is None and multi_template:
+        from .multi import MultiTemplateMFT
+        tracker = MultiTemplateMFT(configs[0], device=device)
     if tracker is None:
         tracker = configs[0].tracker_class(configs[0])
     export, cache_root = Path(export), Path(cache_root)
@@ -363,9 +411,11 @@ def run_dataset(dataset_conf, configs, export, cache_root, mode="both", cont=Fal
             flow_name = configs[0].flow_config.name
             assert flow_name
             cache_dir = cache_root / str(dataset_conf.name) / str(flow_name) / name
-            shutil.rmtree(cache_dir, ignore_errors=True)
-            cache_dir.mkdir(parents=True, exist_ok=True)
-            cache = make_cache(cache_dir, ram_cache_limit * 1e3, gpu_cache_limit * 1e3)
+            cache = None
+            if not multi_template:
+                shutil.rmtree(cache_dir, ignore_errors=True)
+                cache_dir.mkdir(parents=True, exist_ok=True)
+                cache = make_cache(cache_dir, ram_cache_limit * 1e3, gpu_cache_limit * 1e3)
             for query_mode in modes:
                 query_points = np.asarray(seq["data"][query_mode]["query_points"])[0].astype(np.int64)
                 if query_mode == "first" and write_flow and 0 not in np.unique(query_points[:, 0]):
@@ -384,14 +434,24 @@ def run_dataset(dataset_conf, configs, export, cache_root, mode="both", cont=Fal
                             flowou_dir.mkdir(parents=True, exist_ok=True)
                             for frame_i, meta in metas.items():
                                 meta.result.write(flowou_dir / f"0--{frame_i}.flowouX16.pkl")
-                    out = run_sequence(tracker, video, query_points, query_mode, flow_cache=cache, device=device, on_run=on_run,
-                                       debug=debug)
+
+                    def on_result(start_frame, direction, frame_i, result, _cfg=cfg, _mode=query_mode):
+                        if start_frame == 0 and _mode == "first" and write_flow and direction == "forward":
+                            flowou_dir = export / _cfg.name / "flowous" / name
+                            flowou_dir.mkdir(parents=True, exist_ok=True)
+                            result.write(flowou_dir / f"0--{frame_i}.flowouX16.pkl")
+                    if multi_template:
+                        out = run_sequence_multi(tracker, video, query_points, query_mode, device=device, on_result=on_result)
+                    else:
+                        out = run_sequence(tracker, video, query_points, query_mode, flow_cache=cache, device=device,
+                                           on_run=on_run, debug=debug)
                     assert out["tracks"].shape[0] == 1 and out["tracks"].shape[3] == 2 and out["tracks"].ndim == 4
                     with open(path, "wb") as f:
                         pickle.dump(out, f)
                     done.append(dict(sequence=name, mode=query_mode, tracker=cfg.name, path=path, skipped=False))
-            shutil.rmtree(cache_dir, ignore_errors=True)
-            cache.clear()
+            if cache is not None:
+                shutil.rmtree(cache_dir, ignore_errors=True)
+                cache.clear()
     return done
 
 

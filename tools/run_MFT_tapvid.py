@@ -39,6 +39,8 @@ def main():
     ap.add_argument("--synthetic", type=int, default=0, metavar="N",
                     help="no dataset: N seeded synthetic 256 x 256 sequences written as a TAP-Vid pickle, seeded synthetic weights")
     ap.add_argument("--synthetic-frames", type=int, default=40)
+    ap.add_argument("--multi-template", action="store_true",
+                    help="track all start frames of a sequence in one lockstep pass per direction (mft_amd/multi.py); no flow cache")
     a = ap.parse_args()
     from mft_amd import tapvid
     from mft_amd.config import load_config
@@ -62,10 +64,12 @@ def main():
         assert c.flow_config == configs[0].flow_config
     t0 = time.perf_counter()
     done = tapvid.run_dataset(dconf, configs, a.export, a.cache, mode=a.mode, cont=a.cont, seqs=a.seq, write_flow=a.write_flow,
-                              ram_cache_limit=a.ram_cache_limit, gpu_cache_limit=a.gpu_cache_limit, debug=a.debug)
+                              ram_cache_limit=a.ram_cache_limit, gpu_cache_limit=a.gpu_cache_limit, debug=a.debug,
+                              multi_template=a.multi_template)
     dt = time.perf_counter() - t0
     summary = {"dataset": str(dconf.name), "scaling": dconf.scaling, "results": len(done),
-               "skipped": sum(d["skipped"] for d in done), "seconds": dt}
+               "skipped": sum(d["skipped"] for d in done), "seconds": dt,
+               "multi_template": bool(a.multi_template)}
     if not a.no_eval:
         m = tapvid.evaluate_dataset(dconf, configs, a.export, mode=a.mode)
         summary["metrics"] = {mode: {name: {k: float(np.mean([r[k] for r in rows])) for k in
