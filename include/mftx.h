@@ -376,6 +376,32 @@ int mftx_raft_refine_gather(mftx_raft *r, int P, int h, int w, int iters, const 
                             const float *flow_init, int pad_left, int pad_right, int pad_top, int pad_bottom,
                             float *flow, float *occl, float *sigma, float *packed, float *flow_lr_out,
                             void *workspace, size_t workspace_bytes, void *stream);
+/* What a refinement computes from its LEFT frame alone, once per frame instead of once per pair (a cached frame is the left frame of
+ * up to seven later pairs, the template of one in every step): for one frame's fmap [h*w][256] and inp [h*w][128] it writes
+ *   ctx_zr1 [h*w][256], ctx_q1 [h*w][128], ctx_zr2 [h*w][256], ctx_q2 [h*w][128]   the context features' part of the SepConvGRU gate
+ *                                      sums + bias (horizontal pass z | r, q; vertical pass z | r, q), fp32 (all four, or none);
+ *   fmap_split [h*w][256]              the mftx_split_weights form of fmap (optional; fmap may be NULL without it)
+ * with the kernels mftx_raft_refine runs for them inside a batch -- they are batch-invariant: the same bits.  Needs the split
+ * arithmetic and, for the context parts, MFTX_RAFT_OPT_TILE_CONV pinned to 0 or 2 (with 1 the batch would choose the kernel family;
+ * MFTX_E_STATE).  scratch: mftx_raft_frame_prepare_bytes(h, w) bytes, 256-byte aligned (the split form of inp). */
+size_t mftx_raft_frame_prepare_bytes(int h, int w);
+int mftx_raft_frame_prepare(mftx_raft *r, int h, int w, const float *fmap, const float *inp, float *ctx_zr1, float *ctx_q1,
+                            float *ctx_zr2, float *ctx_q2, void *fmap_split, void *scratch, size_t scratch_bytes, void *stream);
+/* mftx_raft_refine_gather with the prepared parts of the pairs' frames, each optional (NULL): ctx_parts = 4 P pointers, pair b's
+ * ctx_zr1, ctx_q1, ctx_zr2, ctx_q2 at ctx_parts[4 b .. 4 b + 3]; fmap1_split = P pointers, the split form of fmap1[b];
+ * fmap2_split = the split form of the ONE second map all pairs share (MFTX_E_ARG otherwise).  The context parts are read where they
+ * lie (through a pointer table in the workspace, rewritten on every call: captured graphs stay valid) where each SepConvGRU pass
+ * runs as one kernel (MFTX_RAFT_OPT_FUSE_GRU on tile-resident layers); otherwise they are ignored and computed as ever.  The
+ * caller vouches that the parts were prepared from the same maps with the same MFTX_RAFT_OPT_TILE_CONV.  Same bits as without. */
+int mftx_raft_refine_gather_ex(mftx_raft *r, int P, int h, int w, int iters, const float *const *fmap1,
+                               const float *const *fmap2, const float *const *net, const float *const *inp,
+                               const float *const *ctx_parts, const void *const *fmap1_split, const void *fmap2_split,
+                               const float *flow_init, int pad_left, int pad_right, int pad_top, int pad_bottom,
+                               float *flow, float *occl, float *sigma, float *packed, float *flow_lr_out,
+                               void *workspace, size_t workspace_bytes, void *stream);
+/* The register split of the tile-resident volume kernel's query loads, over a buffer: every 8 floats -> [hi x 8 | lo x 8] (tests:
+ * equal to mftx_split_weights value for value, which is what lets a prepared split map stand in for it). */
+int mftx_volume_query_split(const float *in, void *out, long long n_floats, void *stream);
 
 /* ---- a3: feature / context encoder (BasicEncoder, core/extractor.py:118-195) ---------
  * Replaces fnet / cnet of RAFT.forward (core/raft.py:122-149) incl. RAFTWrapper's

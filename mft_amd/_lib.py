@@ -97,6 +97,14 @@ SIGNATURES = {
                                           C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mftx_raft_refine_gather_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             _PP, _PP, _PP, _PP, _PP, _PP, C.c_void_p, C.c_void_p,
+                                             C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mftx_raft_frame_prepare_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mftx_raft_frame_prepare": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p]),
+    "mftx_volume_query_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "mftx_encoder_create": (C.c_int, [_PP, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mftx_encoder_destroy": (None, [C.c_void_p]),
     "mftx_encoder_set_graph": (C.c_int, [C.c_void_p, C.c_int]),

@@ -145,8 +145,10 @@ constexpr int MFTX_MAX_GATHER = 16;
 struct PairPtrs { const float *p[MFTX_MAX_GATHER]; };
 // f1p (optional): pair bz's query features at f1p->p[bz] instead of f1 + bz * N * 256; f2_bstride: floats between the pairs'
 // split target maps in f2s (0: every pair correlates against the same map)
+// f1_split: the query features (f1 / f1p) are in split form already (mftx_raft_frame_prepare)
 int launch_volume_tile(const float *f1, const float *f2s, int P, int h, int w, float *const lvl[4], hipStream_t s,
-                       const PairPtrs *f1p = nullptr, long long f2_bstride = -1);
+                       const PairPtrs *f1p = nullptr, long long f2_bstride = -1, bool f1_split = false);
+int launch_volume_query_split(const float *in, void *out, long long n_floats, hipStream_t s);    // vt_split8 over a buffer (tests)
 int launch_corr_lookup(const float *const lvl[4], const float *coords, int P, int h, int w,
                        float *out, int ld_out, hipStream_t s);
 // lookup fused into convc1 (csrc/lookup_convc1.hip): out = relu(convc1(lookup(coords)) + bias), [M][ld_out], fp32 or split form
@@ -178,6 +180,9 @@ struct GruHalfLaunch {
     const float *h_in; int ld_hin; const float *mo; int ld_mo;      // h and the motion features, split form, 128 channels each
     const void *wzr, *wq;                                           // launch_pack_tile_conv streams (N = 256 / 128, cin = 256)
     const float *pre_zr, *pre_q;                                    // context parts + bias [M][256] / [M][128]
+    // ... or, per pair, wherever a DEVICE table says: ctx[4 b + 2 pass] / ctx[4 b + 2 pass + 1] = pair b's [N][256] / [N][128]
+    // (the engine: the table lives in the workspace and is rewritten before every refinement, outside the captured graph)
+    const float *const *ctx;
     float *z; const float *hf_in; float *hf_out;                    // z scratch [M][128]; h in fp32 [M][128]: read here, written there
     float *h_out; int ld_hout;                                      // new h in split form (a different buffer than h_in)
     int P, h, w, pass;

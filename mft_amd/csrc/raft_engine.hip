@@ -21,11 +21,19 @@ namespace mftx {
 // fp32 into hf [M][128], the copy the GRU's gate algebra reads
 // gathered != 0: pair b's net / inp maps at netp.p[b] / inpp.p[b] (mftx_raft_refine_gather) instead of net + b N 128
 struct InitGather { int on; PairPtrs netp, inpp; };
+// Where the fused GRU pass finds every pair's context parts (GruHalfLaunch.ctx): table[4 b + k], k = zr pass 0, q pass 0, zr pass
+// 1, q pass 1.  The refinement's middle is a captured graph whose kernel arguments are frozen, this kernel runs in front of it on
+// every call: it writes the table -- the parts the caller supplied (mftx_raft_refine_gather_ex), or the workspace's own.
+struct CtxTable { const float **table; const float *own[4]; int supplied; PairPtrs parts[4]; };
 __global__ void init_state_kernel(const float *__restrict__ net, const float *__restrict__ inp,
                                   const float *__restrict__ flow_init, float *hx, float *hf, float *coords1, int M, int h,
-                                  int w, InitGather ga) {
+                                  int w, InitGather ga, CtxTable ct) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;  // over M*64 float4 slots
     if (i >= (long long)M * 64) return;
+    if (ct.table != nullptr && i < (long long)(M / (h * w)) * 4) {
+        const int b = (int)(i >> 2), k = (int)(i & 3);
+        ct.table[i] = ct.supplied ? ct.parts[k].p[b] : ct.own[k] + (long long)b * h * w * ((k & 1) ? 128 : 256);
+    }
     const int m = (int)(i >> 6), q = (int)(i & 63);
     if (ga.on) {                                     // (this pair's maps: the index below becomes the cell inside the pair)
         const int b = m / (h * w);
@@ -135,6 +143,7 @@ struct Workspace {
     float *f2s;                    // split form of fmap2 (B operand of the volume GEMM in split arithmetic)
     float *hf;                     // split arithmetic: fp32 copy of h [M][128] (hx itself is in split form)
     float *hb, *hfb;               // split arithmetic: h between the two passes of the fused GRU kernel [M][128]: split form, fp32
+    const float **ctx;             // split arithmetic: the pairs' context parts for the fused GRU kernel, [P][4] pointers (CtxTable)
     int ld_corr;                   // 324: the lookup's features stay fp32 (the lookup is HBM-bound; convc1 splits them in registers)
     size_t bytes;
 };
@@ -172,6 +181,7 @@ static Workspace carve(void *base, int P, int h, int w, bool ondemand = false, b
     ws.hf = take(split ? M * 128 : 0);
     ws.hb = take(split ? M * 128 : 0);
     ws.hfb = take(split ? M * 128 : 0);
+    ws.ctx = reinterpret_cast<const float **>(take(split ? (size_t)P * 8 : 0));
     ws.bytes = off;
     return ws;
 }
@@ -399,7 +409,39 @@ static mftx_conv_desc conv_desc(const float *a0, int lda0, int c0, const float *
 
 // gather (optional): the pairs' maps through per-pair pointers (fmap1 / fmap2 / net / inp are then unused); f2_shared: every
 // pair has the SAME second feature map (gather->f2.p[0])
-struct RefineGather { PairPtrs f1, f2, net, inp; bool f2_shared; };
+// per-frame parts computed ahead of the pairs (mftx_raft_frame_prepare), all optional: ctx[k] the pairs' context parts (k as in
+// CtxTable), f1s the split form of the first maps, f2s the split form of the shared second map
+struct RefineGather { PairPtrs f1, f2, net, inp; bool f2_shared; bool has_ctx, has_f1s; PairPtrs ctx[4], f1s; const float *f2s; };
+
+// The context features' third of the four GRU gate sums (+ bias): zr[pass] [M][256], q[pass] [M][128] from `inp` ([M][128] at stride
+// ld; split form when sp).  ONE place for the refinement and for mftx_raft_frame_prepare: the same kernels, the same bits.
+static int launch_context_parts(const mftx_raft *r, bool tiles_on, bool sp, const float *inp, int ld, int P, int h, int w,
+                                float *const zr[2], float *const q[2], hipStream_t s) {
+    const float *const *W = r->w;
+    const float *const *G = r->wg;
+    for (int pass = 0; pass < 2; ++pass) {
+        const int kh = pass ? 5 : 1, kw = pass ? 1 : 5;
+        const int slot[2] = {pass ? W_ZR2_INP : W_ZR1_INP, pass ? W_Q2_INP : W_Q1_INP};
+        const float *bias[2] = {W[pass ? B_ZR2 : B_ZR1], W[pass ? B_Q2 : B_Q1]};
+        float *out[2] = {zr[pass], q[pass]};
+        for (int k = 0; k < 2; ++k) {
+            const int N = k ? 128 : 256;
+            if (tiles_on && r->wt[slot[k]]) {
+                TileConvLaunch t{};
+                t.a0 = inp; t.lda0 = ld; t.cin = 128; t.wf = r->wt[slot[k]]; t.bias = bias[k];
+                t.P = P; t.h = h; t.w = w; t.N = N; t.kh = kh; t.kw = kw; t.epi = 0;
+                t.cells = r->opt[MFTX_RAFT_OPT_TILE_CELLS];
+                t.out = out[k]; t.ldo = N;
+                TRY(launch_tile_conv(t, s));
+            } else {
+                mftx_conv_desc d = conv_desc(inp, ld, 128, nullptr, 0, 0, G[slot[k]], bias[k], out[k], N, P, h, w, N, kh, kw, 0);
+                d.arith = r->arith; d.a_split = sp; d.out_split = false;
+                TRY(launch_conv(d, s));
+            }
+        }
+    }
+    return 0;
+}
 static int refine_impl(mftx_raft *r, int P, int h, int w, int iters, const float *fmap1,
                                 const float *fmap2, const float *net, const float *inp, const float *flow_init,
                                 int pad_left,
@@ -454,18 +496,45 @@ static int refine_impl(mftx_raft *r, int P, int h, int w, int iters, const float
         // gathered pairs (split arithmetic, tile-resident volume: checked by the caller): the second maps are split into the
         // workspace -- once when all pairs share one -- and the volume kernel takes every pair's first map where it lies
         const long long pair_floats = (long long)N * 256;
-        if (gather->f2_shared) TRY(launch_split_weights(gather->f2.p[0], ws.f2s, pair_floats, s));
+        // (a frame prepared ahead brings its split map along: nothing to split for the second map, nothing to split in the volume
+        // kernel's K loop for the first)
+        const float *f2s = ws.f2s;
+        if (gather->f2_shared && gather->f2s) f2s = gather->f2s;
+        else if (gather->f2_shared) TRY(launch_split_weights(gather->f2.p[0], ws.f2s, pair_floats, s));
         else for (int b = 0; b < P; ++b) TRY(launch_split_weights(gather->f2.p[b], ws.f2s + b * pair_floats, pair_floats, s));
-        TRY(launch_volume_tile(nullptr, ws.f2s, P, h, w, ws.lvl, s, &gather->f1, gather->f2_shared ? 0 : pair_floats));
+        TRY(launch_volume_tile(nullptr, f2s, P, h, w, ws.lvl, s, gather->has_f1s ? &gather->f1s : &gather->f1, gather->f2_shared ? 0 : pair_floats,
+                               gather->has_f1s));
     }
     else TRY(launch_corr_pyramid(fmap1, fmap2, P, 256, h, w, ws.lvl, s, r->arith == MFTX_ARITH_SPLIT ? ws.f2s : nullptr, r->opt[MFTX_RAFT_OPT_TILE_VOLUME]));
+    // Layers whose input tile fits a CU's LDS run on the tile-resident kernel (csrc/tile_conv.hip) when its weight streams are set
+    // (option value 2: whatever the batch; 1, the default: only when the tiles fill the chip -- at 256 x 256 pixels or one pair
+    // per GPU the ring-buffered kernel's small tiles win)
+    const bool tiles_on = SP && r->opt[MFTX_RAFT_OPT_TILE_CONV] != 0 &&
+                          (r->opt[MFTX_RAFT_OPT_TILE_CONV] == 2 ||
+                           (tile_conv_fills_chip(P, h, w, 3, 3) && tile_conv_fills_chip(P, h, w, 1, 5) && tile_conv_fills_chip(P, h, w, 5, 1)));
+    auto tile_w = [&](int slot) -> const void * { return tiles_on ? r->wt[slot] : nullptr; };
+    // SepConvGRU as one kernel per pass
+    // (decided ONCE for both passes: they hand h over through the ping-pong pair hx/hf <-> hb/hfb, so one fused and one
+    // unfused pass would read a buffer the other never wrote -- a partial set of tile weights runs both passes unfused)
+    const bool gru_fused = tile_w(W_ZR1_DYN) && tile_w(W_Q1_DYN) && tile_w(W_ZR2_DYN) && tile_w(W_Q2_DYN) &&
+                           r->opt[MFTX_RAFT_OPT_FUSE_GRU] != 0;
+    // context parts that came with the pairs are honoured where the fused pass reads them through the table; elsewhere they are
+    // computed here as ever
+    const bool ctx_supplied = gather && gather->has_ctx && gru_fused;
     {
         const long long slots = (long long)M * 64;
         ProfScope prof(PC_GLUE, s, 0);
         InitGather ga{};
         if (gather) { ga.on = 1; ga.netp = gather->net; ga.inpp = gather->inp; }
+        CtxTable ct{};
+        if (gru_fused) {
+            ct.table = ws.ctx;
+            ct.own[0] = ws.pre_zr[0]; ct.own[1] = ws.pre_q[0]; ct.own[2] = ws.pre_zr[1]; ct.own[3] = ws.pre_q[1];
+            ct.supplied = ctx_supplied ? 1 : 0;
+            if (ctx_supplied) for (int k = 0; k < 4; ++k) ct.parts[k] = gather->ctx[k];
+        }
         hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, net, inp,
-                           flow_init, ws.hx, SP ? ws.hf : nullptr, ws.coords1, M, h, w, ga);
+                           flow_init, ws.hx, SP ? ws.hf : nullptr, ws.coords1, M, h, w, ga, ct);
         TRY(check_launch("init_state"));
     }
     float *flow_lr = flow_lr_out ? flow_lr_out : ws.flow_lr;
@@ -476,13 +545,7 @@ static int refine_impl(mftx_raft *r, int P, int h, int w, int iters, const float
     // The gate convolutions are linear in their input [h | inp | motion] and `inp` does not change
     // over the iterations (core/raft.py:146-149): its third of every gate sum (+ bias) is computed
     // once here and enters the per-iteration GEMMs as an epilogue addend.  Same terms, summed once.
-    // Layers whose input tile fits a CU's LDS run on the tile-resident kernel (csrc/tile_conv.hip) when its weight streams are set
-    // (option value 2: whatever the batch; 1, the default: only when the tiles fill the chip -- at 256 x 256 pixels or one pair
-    // per GPU the ring-buffered kernel's small tiles win)
-    const bool tiles_on = SP && r->opt[MFTX_RAFT_OPT_TILE_CONV] != 0 &&
-                          (r->opt[MFTX_RAFT_OPT_TILE_CONV] == 2 ||
-                           (tile_conv_fills_chip(P, h, w, 3, 3) && tile_conv_fills_chip(P, h, w, 1, 5) && tile_conv_fills_chip(P, h, w, 5, 1)));
-    auto tile_w = [&](int slot) -> const void * { return tiles_on ? r->wt[slot] : nullptr; };
+    // (a frame's parts computed when it was encoded -- mftx_raft_frame_prepare -- arrive through the table instead)
     auto tile_layer = [&](const float *a0, int lda0, const float *a1, int lda1, const void *wf, const float *bias, int N, int kh, int kw, int epi) {
         TileConvLaunch t{};
         t.a0 = a0; t.lda0 = lda0; t.a1 = a1; t.lda1 = lda1; t.cin = a1 ? 256 : 128; t.wf = wf; t.bias = bias;
@@ -490,20 +553,7 @@ static int refine_impl(mftx_raft *r, int P, int h, int w, int iters, const float
         t.cells = r->opt[MFTX_RAFT_OPT_TILE_CELLS];
         return t;
     };
-    for (int pass = 0; pass < 2; ++pass) {
-        const int kh = pass ? 5 : 1, kw = pass ? 1 : 5;
-        const int szr = pass ? W_ZR2_INP : W_ZR1_INP, sq = pass ? W_Q2_INP : W_Q1_INP;
-        if (tile_w(szr)) {
-            TileConvLaunch t = tile_layer(ws.hx + 128, 384, nullptr, 0, tile_w(szr), W[pass ? B_ZR2 : B_ZR1], 256, kh, kw, 0);
-            t.out = ws.pre_zr[pass]; t.ldo = 256;
-            TRY(launch_tile_conv(t, s));
-        } else TRY(launch_conv(gemm(conv_desc(ws.hx + 128, 384, 128, nullptr, 0, 0, G[szr], W[pass ? B_ZR2 : B_ZR1], ws.pre_zr[pass], 256, P, h, w, 256, kh, kw, 0), true, false), s));
-        if (tile_w(sq)) {
-            TileConvLaunch t = tile_layer(ws.hx + 128, 384, nullptr, 0, tile_w(sq), W[pass ? B_Q2 : B_Q1], 128, kh, kw, 0);
-            t.out = ws.pre_q[pass]; t.ldo = 128;
-            TRY(launch_tile_conv(t, s));
-        } else TRY(launch_conv(gemm(conv_desc(ws.hx + 128, 384, 128, nullptr, 0, 0, G[sq], W[pass ? B_Q2 : B_Q1], ws.pre_q[pass], 128, P, h, w, 128, kh, kw, 0), true, false), s));
-    }
+    if (!ctx_supplied) TRY(launch_context_parts(r, tiles_on, SP, ws.hx + 128, 384, P, h, w, ws.pre_zr, ws.pre_q, s));
     const float *lv[4] = {ws.lvl[0], ws.lvl[1], ws.lvl[2], ws.lvl[3]};
     const int strips = cdiv(w, F1_CELLS);
     // The coordinates the iteration works on.  With the flow branch and the flow head both fused, an iteration's update is
@@ -605,10 +655,6 @@ static int refine_impl(mftx_raft *r, int P, int h, int w, int iters, const float
         if (two_pass) TRY(launch_tile_conv2p(ws.corflo, 256, r->wt[W_CONV], W[B_CONV], ws.hx + 256, 384, 126, P, h, w, r->opt[MFTX_RAFT_OPT_TILE_CELLS], s));
         else TRY(launch_conv(gemm(conv_desc(ws.corflo, 256, 256, nullptr, 0, 0, G[W_CONV], W[B_CONV], ws.hx + 256, 384, P, h, w, 126, 3, 3, 1), true, true), s));
         // SepConvGRU (core/update.py:108-123): horizontal 1x5 then vertical 5x1
-        // (decided ONCE for both passes: they hand h over through the ping-pong pair hx/hf <-> hb/hfb, so one fused and one
-        // unfused pass would read a buffer the other never wrote -- a partial set of tile weights runs both passes unfused)
-        const bool gru_fused = tile_w(W_ZR1_DYN) && tile_w(W_Q1_DYN) && tile_w(W_ZR2_DYN) && tile_w(W_Q2_DYN) &&
-                               r->opt[MFTX_RAFT_OPT_FUSE_GRU] != 0;
         for (int pass = 0; pass < 2; ++pass) {
             const int kh = pass ? 5 : 1, kw = pass ? 1 : 5;
             const int szr = pass ? W_ZR2_DYN : W_ZR1_DYN, sq = pass ? W_Q2_DYN : W_Q1_DYN;
@@ -617,7 +663,7 @@ static int refine_impl(mftx_raft *r, int P, int h, int w, int iters, const float
                 // hx -> hb in the horizontal pass and back in the vertical one (a tile's halo cells are its neighbours' outputs)
                 GruHalfLaunch g{};
                 g.h_in = pass ? ws.hb : ws.hx; g.ld_hin = pass ? 128 : 384; g.h_out = pass ? ws.hx : ws.hb; g.ld_hout = pass ? 384 : 128;
-                g.mo = ws.hx + 256; g.ld_mo = 384; g.wzr = tile_w(szr); g.wq = tile_w(sq); g.pre_zr = ws.pre_zr[pass]; g.pre_q = ws.pre_q[pass];
+                g.mo = ws.hx + 256; g.ld_mo = 384; g.wzr = tile_w(szr); g.wq = tile_w(sq); g.pre_zr = ws.pre_zr[pass]; g.pre_q = ws.pre_q[pass]; g.ctx = ws.ctx;
                 g.z = ws.z; g.hf_in = pass ? ws.hfb : ws.hf; g.hf_out = pass ? ws.hf : ws.hfb; g.P = P; g.h = h; g.w = w; g.pass = pass; g.cells = r->opt[MFTX_RAFT_OPT_TILE_CELLS];
                 TRY(launch_gru_half(g, s));
                 continue;
@@ -711,7 +757,7 @@ static int refine_impl(mftx_raft *r, int P, int h, int w, int iters, const float
         key.v[4] = reinterpret_cast<uintptr_t>(workspace); key.v[5] = reinterpret_cast<uintptr_t>(flow_lr_out);
         key.v[6] = (uintptr_t)AR; key.v[7] = reinterpret_cast<uintptr_t>(r->wfused); key.v[8] = reinterpret_cast<uintptr_t>(s);
         key.v[9] = reinterpret_cast<uintptr_t>(r->wflow); key.v[10] = reinterpret_cast<uintptr_t>(r->wt[W_ZR1_DYN]); key.v[11] = reinterpret_cast<uintptr_t>(r->wproj);
-        key.v[12] = reinterpret_cast<uintptr_t>(r->wou);
+        key.v[12] = reinterpret_cast<uintptr_t>(r->wou); key.v[13] = ctx_supplied ? 1 : 0;       // (with the parts supplied the sequence is four launches shorter)
         TRY(r->graphs->run(key, s, core));
     } else {
         TRY(core());
@@ -734,6 +780,16 @@ extern "C" int mftx_raft_refine_gather(mftx_raft *r, int P, int h, int w, int it
                                        const float *flow_init, int pad_left, int pad_right, int pad_top, int pad_bottom,
                                        float *flow, float *occl, float *sigma, float *packed, float *flow_lr_out,
                                        void *workspace, size_t workspace_bytes, void *stream) {
+    return mftx_raft_refine_gather_ex(r, P, h, w, iters, fmap1, fmap2, net, inp, nullptr, nullptr, nullptr, flow_init, pad_left, pad_right, pad_top,
+                                      pad_bottom, flow, occl, sigma, packed, flow_lr_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mftx_raft_refine_gather_ex(mftx_raft *r, int P, int h, int w, int iters, const float *const *fmap1,
+                                          const float *const *fmap2, const float *const *net, const float *const *inp,
+                                          const float *const *ctx_parts, const void *const *fmap1_split, const void *fmap2_split,
+                                          const float *flow_init, int pad_left, int pad_right, int pad_top, int pad_bottom,
+                                          float *flow, float *occl, float *sigma, float *packed, float *flow_lr_out,
+                                          void *workspace, size_t workspace_bytes, void *stream) {
     if (!r || r->magic != RAFT_MAGIC) return fail(MFTX_E_STATE, "raft_refine_gather: bad handle");
     if (!fmap1 || !fmap2 || !net || !inp) return fail(MFTX_E_ARG, "raft_refine_gather: null pointer");
     if (P < 1 || P > MFTX_MAX_GATHER) return fail(MFTX_E_ARG, "raft_refine_gather: 1 .. %d pairs", MFTX_MAX_GATHER);
@@ -747,8 +803,82 @@ extern "C" int mftx_raft_refine_gather(mftx_raft *r, int P, int h, int w, int it
         g.f1.p[b] = fmap1[b]; g.f2.p[b] = fmap2[b]; g.net.p[b] = net[b]; g.inp.p[b] = inp[b];
         if (fmap2[b] != fmap2[0]) g.f2_shared = false;
     }
+    if (ctx_parts) {
+        for (int i = 0; i < 4 * P; ++i)
+            if (!ctx_parts[i] || !aligned16(ctx_parts[i])) return fail(MFTX_E_ALIGN, "raft_refine_gather: context part %d of pair %d null or not 16-byte aligned", i & 3, i >> 2);
+        g.has_ctx = true;
+        for (int b = 0; b < P; ++b) for (int k = 0; k < 4; ++k) g.ctx[k].p[b] = ctx_parts[4 * b + k];
+    }
+    if (fmap1_split) {
+        for (int b = 0; b < P; ++b) {
+            if (!fmap1_split[b] || !aligned16(fmap1_split[b])) return fail(MFTX_E_ALIGN, "raft_refine_gather: split map of pair %d null or not 16-byte aligned", b);
+            g.f1s.p[b] = static_cast<const float *>(fmap1_split[b]);
+        }
+        g.has_f1s = true;
+    }
+    if (fmap2_split) {
+        if (!aligned16(fmap2_split)) return fail(MFTX_E_ALIGN, "raft_refine_gather: the second map's split form must be 16-byte aligned");
+        if (!g.f2_shared) return fail(MFTX_E_ARG, "raft_refine_gather: a split second map goes with ONE second map for all pairs");
+        g.f2s = static_cast<const float *>(fmap2_split);
+    }
     return refine_impl(r, P, h, w, iters, nullptr, nullptr, nullptr, nullptr, flow_init, pad_left, pad_right, pad_top, pad_bottom, flow, occl,
                        sigma, packed, flow_lr_out, workspace, workspace_bytes, stream, &g);
+}
+
+// ---------------------------------------------------------------------------
+// per-frame preparation
+// ---------------------------------------------------------------------------
+// [rows][4 c4] fp32 -> split form, by the per-value operations of init_state_kernel (store_split4v)
+__global__ void split_rows_kernel(const float *__restrict__ in, float *__restrict__ out, long long slots, int c4) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;  // over rows * c4 float4 slots
+    if (i >= slots) return;
+    const long long m = i / c4;
+    const int q = (int)(i - m * c4);
+    store_split4v(out + m * 4 * c4, 4 * q, reinterpret_cast<const float4 *>(in)[i]);
+}
+
+extern "C" size_t mftx_raft_frame_prepare_bytes(int h, int w) {
+    if (h <= 0 || w <= 0) return 0;
+    return ((size_t)h * w * 128 * sizeof(float) + 255) & ~size_t(255);
+}
+
+extern "C" int mftx_raft_frame_prepare(mftx_raft *r, int h, int w, const float *fmap, const float *inp, float *ctx_zr1, float *ctx_q1,
+                                       float *ctx_zr2, float *ctx_q2, void *fmap_split, void *scratch, size_t scratch_bytes, void *stream) {
+    if (!r || r->magic != RAFT_MAGIC) return fail(MFTX_E_STATE, "raft_frame_prepare: bad handle");
+    if (h < 16 || w < 16 || (long long)h * w > (1ll << 24)) return fail(MFTX_E_ARG, "raft_frame_prepare: bad size");
+    const bool want_ctx = ctx_zr1 || ctx_q1 || ctx_zr2 || ctx_q2;
+    if (!want_ctx && !fmap_split) return fail(MFTX_E_ARG, "raft_frame_prepare: nothing to write");
+    if (r->arith != MFTX_ARITH_SPLIT || r->opt[MFTX_RAFT_OPT_PRESPLIT] == 0)
+        return fail(MFTX_E_STATE, "raft_frame_prepare: needs the split arithmetic with split-form activations");
+    hipStream_t s = (hipStream_t)stream;
+    const long long N = (long long)h * w;
+    if (fmap_split) {
+        if (!fmap) return fail(MFTX_E_ARG, "raft_frame_prepare: a split map needs fmap");
+        TRY(launch_split_weights(fmap, fmap_split, N * 256, s));
+    }
+    if (!want_ctx) return 0;
+    if (!inp || !ctx_zr1 || !ctx_q1 || !ctx_zr2 || !ctx_q2 || !scratch) return fail(MFTX_E_ARG, "raft_frame_prepare: the context parts need inp, all four outputs and the scratch");
+    // the batches this frame will ride in must run the kernel family chosen here, whatever their size: a pinned choice only
+    if (r->opt[MFTX_RAFT_OPT_TILE_CONV] == 1)
+        return fail(MFTX_E_STATE, "raft_frame_prepare: MFTX_RAFT_OPT_TILE_CONV must be pinned (0 or 2), the batch decides otherwise");
+    if (!aligned16(inp) || !aligned16(ctx_zr1) || !aligned16(ctx_q1) || !aligned16(ctx_zr2) || !aligned16(ctx_q2) ||
+        (reinterpret_cast<uintptr_t>(scratch) & 255))
+        return fail(MFTX_E_ALIGN, "raft_frame_prepare: maps must be 16-byte and the scratch 256-byte aligned");
+    if (scratch_bytes < mftx_raft_frame_prepare_bytes(h, w))
+        return fail(MFTX_E_WORKSPACE, "raft_frame_prepare: scratch %zu < %zu bytes", scratch_bytes, mftx_raft_frame_prepare_bytes(h, w));
+    float *inps = static_cast<float *>(scratch);
+    {
+        const long long slots = N * 32;
+        hipLaunchKernelGGL(split_rows_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, inp, inps, slots, 32);
+        TRY(check_launch("split_rows"));
+    }
+    float *const zr[2] = {ctx_zr1, ctx_zr2}, *const q[2] = {ctx_q1, ctx_q2};
+    return launch_context_parts(r, r->opt[MFTX_RAFT_OPT_TILE_CONV] == 2, true, inps, 128, 1, h, w, zr, q, s);
+}
+
+extern "C" int mftx_volume_query_split(const float *in, void *out, long long n_floats, void *stream) {
+    if (!in || !out) return fail(MFTX_E_ARG, "volume_query_split: null pointer");
+    return launch_volume_query_split(in, out, n_floats, (hipStream_t)stream);
 }
 
 extern "C" int mftx_raft_graph_stats(const mftx_raft *r, unsigned long long *captures, unsigned long long *replays) {

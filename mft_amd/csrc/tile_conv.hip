@@ -426,6 +426,8 @@ struct GruHalfArgs {
     const float *mo; int ld_mo;         // motion features, split form, 128 channels
     const void *wzr, *wq;               // mftx_pack_tile_conv_weights streams: [z | r] (N = 256) and q (N = 128), cin = 256
     const float *pre_zr, *pre_q;        // the gates' context parts + bias (pre-activation addends): [M][256], [M][128]
+    const float *const *ctx;            // or null; else pair b's parts at ctx[4 b + 2 pass], ctx[4 b + 2 pass + 1]: [N][256], [N][128]
+    int pass;
     float *z;                           // scratch [M][128]
     const float *hf_in; float *hf_out;  // h in fp32 [M][128]: read from one buffer, written to another, like the split form
     float *h_out; int ld_hout;          // new h, split form
@@ -483,6 +485,13 @@ __global__ __launch_bounds__(512, 2) void gru_half_kernel(GruHalfArgs p) {
     const int olo = n_along > 1 ? t_along * p.step : 0, ohi = n_along > 1 ? min(len_along, olo + p.step) : len_along;
     const int x0 = HORIZ ? r0 : tx_ * TW, y0 = HORIZ ? ty_ * TH : r0;
     const long long img_base = (long long)img * p.h * p.w;
+    // the context parts of this workgroup's pair: one wave-uniform load of two pointers from the table (indexed below with the
+    // cell index of the whole batch, like the one-tensor form: hence the pair's offset taken off)
+    const float *pre_zr = p.pre_zr, *pre_q = p.pre_q;
+    if (p.ctx != nullptr) {
+        pre_zr = p.ctx[4 * img + 2 * p.pass] - img_base * 256;
+        pre_q = p.ctx[4 * img + 2 * p.pass + 1] - img_base * 128;
+    }
     const uint4 *__restrict__ w1 = reinterpret_cast<const uint4 *>(p.wzr) + (long long)((wv ^ 4) * G1::STEPS) * 128 + lane;   // (r for waves 0-3: see below)
     const int nt2 = wv % G2::NT, ks2 = wv / G2::NT;
     const uint4 *__restrict__ w2 = reinterpret_cast<const uint4 *>(p.wq) + (long long)((nt2 * G2::KS + ks2) * G2::STEPS) * 128 + lane;
@@ -580,7 +589,7 @@ __global__ __launch_bounds__(512, 2) void gru_half_kernel(GruHalfArgs p) {
             tc_f32x4 a[4], hh[4];
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
-                a[b] = *reinterpret_cast<const tc_f32x4 *>(p.pre_zr + cell * 256 + 128 + n0 + 8 * b);
+                a[b] = *reinterpret_cast<const tc_f32x4 *>(pre_zr + cell * 256 + 128 + n0 + 8 * b);
                 hh[b] = *reinterpret_cast<const tc_f32x4 *>(p.hf_in + cell * 128 + n0 + 8 * b);
             }
 #pragma unroll
@@ -663,11 +672,11 @@ __global__ __launch_bounds__(512, 2) void gru_half_kernel(GruHalfArgs p) {
         v += *reinterpret_cast<const tc_f32x4 *>(src + CELLS * G2::RED_ROW + 4);
         if (yy < 0 || yy >= p.h || xx < 0 || xx >= p.w || along < olo || along >= ohi) continue;
         const long long cell = img_base + (long long)yy * p.w + xx;
-        u += *reinterpret_cast<const tc_f32x4 *>(p.pre_q + cell * 128 + n0);
-        v += *reinterpret_cast<const tc_f32x4 *>(p.pre_q + cell * 128 + n0 + 4);
+        u += *reinterpret_cast<const tc_f32x4 *>(pre_q + cell * 128 + n0);
+        v += *reinterpret_cast<const tc_f32x4 *>(pre_q + cell * 128 + n0 + 4);
         tc_f32x4 z0 = *reinterpret_cast<const tc_f32x4 *>(p.z + cell * 128 + n0), z1 = *reinterpret_cast<const tc_f32x4 *>(p.z + cell * 128 + n0 + 4);
-        z0 += *reinterpret_cast<const tc_f32x4 *>(p.pre_zr + cell * 256 + n0);
-        z1 += *reinterpret_cast<const tc_f32x4 *>(p.pre_zr + cell * 256 + n0 + 4);
+        z0 += *reinterpret_cast<const tc_f32x4 *>(pre_zr + cell * 256 + n0);
+        z1 += *reinterpret_cast<const tc_f32x4 *>(pre_zr + cell * 256 + n0 + 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) { z0[e] = tc_sigmoid(z0[e]); z1[e] = tc_sigmoid(z1[e]); }
         const float *hrow = p.hf_in + cell * 128 + n0;
@@ -723,7 +732,7 @@ long long gru_half_tiles(int P, int h, int w, int th, int tw, bool horiz) {
 }
 
 int launch_gru_half(const GruHalfLaunch &d, hipStream_t s) {
-    if (!d.h_in || !d.mo || !d.wzr || !d.wq || !d.pre_zr || !d.pre_q || !d.z || !d.hf_in || !d.hf_out || !d.h_out) return fail(MFTX_E_ARG, "gru_half: null pointer");
+    if (!d.h_in || !d.mo || !d.wzr || !d.wq || (!d.ctx && (!d.pre_zr || !d.pre_q)) || !d.z || !d.hf_in || !d.hf_out || !d.h_out) return fail(MFTX_E_ARG, "gru_half: null pointer");
     if (d.P <= 0 || d.h <= 0 || d.w <= 0 || (d.pass != 0 && d.pass != 1)) return fail(MFTX_E_ARG, "gru_half: bad sizes");
     if (d.h_in == d.h_out || d.hf_in == d.hf_out) return fail(MFTX_E_ARG, "gru_half: h is read from one buffer and written to another");
     auto bad_split = [](const float *p, int ld) { return (reinterpret_cast<uintptr_t>(p) & 31) != 0 || (ld % 8) != 0; };
@@ -731,7 +740,7 @@ int launch_gru_half(const GruHalfLaunch &d, hipStream_t s) {
         !aligned16(d.pre_zr) || !aligned16(d.pre_q) || !aligned16(d.z) || !aligned16(d.hf_in) || !aligned16(d.hf_out))
         return fail(MFTX_E_ALIGN, "gru_half: split-form rows are 32-byte aligned with strides in multiples of 8; the rest 16-byte aligned");
     GruHalfArgs a{};
-    a.h_in = d.h_in; a.ld_hin = d.ld_hin; a.mo = d.mo; a.ld_mo = d.ld_mo; a.wzr = d.wzr; a.wq = d.wq; a.pre_zr = d.pre_zr; a.pre_q = d.pre_q;
+    a.h_in = d.h_in; a.ld_hin = d.ld_hin; a.mo = d.mo; a.ld_mo = d.ld_mo; a.wzr = d.wzr; a.wq = d.wq; a.pre_zr = d.pre_zr; a.pre_q = d.pre_q; a.ctx = d.ctx; a.pass = d.pass;
     a.z = d.z; a.hf_in = d.hf_in; a.hf_out = d.hf_out; a.h_out = d.h_out; a.ld_hout = d.ld_hout; a.P = d.P; a.h = d.h; a.w = d.w;
     // R tiles of 128 cells where they fill the chip -- 2 x 64 (a 64-wide map is one tile per row pair: nothing is recomputed) or
     // 4 x 32, whichever needs fewer workgroups --, else of 64 or 32 cells: the same kernel with fewer row tiles per wave, the same bits

@@ -31,7 +31,7 @@ constexpr int VT_TARGETS = 128 * VT_ROW;        // 133 120
 constexpr int VT_LDS = VT_TARGETS + 8 * 1024;   // + a 1 KB transpose slab per wave (level-0 lines, see the epilogue)
 
 struct VolTileArgs {
-    const float *f1;            // [P][N][256] fp32
+    const float *f1;            // [P][N][256] fp32 (volume_tile_kernel<true>: split form, like f2s)
     const float *f2s;           // [P][N][256] split form
     float *lvl0, *lvl1, *lvl2, *lvl3;
     long long s0, s1, s2, s3;   // floats per query cell, per level (pyramid layout of common.h)
@@ -39,7 +39,7 @@ struct VolTileArgs {
     float scale;
     int qchunks, blocks_per_chunk;      // query blocks (of 32) per workgroup
     int ablate;                         // tuning builds only (MFTX_VT_ABLATE): 1 no level-0 stores, 2 no pooled stores, 8 no level-2 / 3 stores
-    int gathered;                       // pair bz's queries at f1p.p[bz] (mftx_raft_refine_gather)
+    int gathered;                       // pair bz's queries at f1p.p[bz] (mftx_raft_refine_gather; <true>: their split form)
     long long f2_bstride;               // floats between the pairs' target maps in f2s (0: shared)
     PairPtrs f1p;
 };
@@ -93,6 +93,10 @@ __device__ __forceinline__ float vt_shr(float v) {
 // ATen's avg_pool2d order: ((a + b) + c + d) * 0.25, a b = top row, c d = bottom row
 __device__ __forceinline__ float vt_pool4(float a, float b, float c, float d) { return (((a + b) + c) + d) * 0.25f; }
 
+// QSPLIT: the query features arrive in split form (mftx_raft_frame_prepare: a frame is the query map of up to seven later
+// pairs) -- a k group's two 16-byte loads ARE the hi x 8 and lo x 8 halves, nothing is split in the K loop.  The same halves
+// (launch_split_weights and vt_split8 round the same way, value for value), the same MFMAs: the same bits.
+template <bool QSPLIT>
 __global__ __launch_bounds__(512, 2) void volume_tile_kernel(VolTileArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char vt_lds[];
     unsigned char *lds = vt_lds;
@@ -167,7 +171,10 @@ __global__ __launch_bounds__(512, 2) void volume_tile_kernel(VolTileArgs p) {
         for (int g = 0; g < 16; ++g) {
             const int set = g & 1;
             vt_f16x8 bh, bl;
-            vt_split8(raw[g % PF][0], raw[g % PF][1], k2048, bh, bl);
+            if constexpr (QSPLIT) {
+                bh = __builtin_bit_cast(vt_f16x8, raw[g % PF][0]);
+                bl = __builtin_bit_cast(vt_f16x8, raw[g % PF][1]);
+            } else vt_split8(raw[g % PF][0], raw[g % PF][1], k2048, bh, bl);
             __builtin_amdgcn_sched_barrier(0);
             if (g + 1 < 16) read_a(g + 1, set ^ 1);
             if (g + PF < 16) {
@@ -341,8 +348,30 @@ static int vt_num_cus() {
 
 bool volume_tile_applicable(int C) { return C == VT_C; }
 
-// f1: raw fp32 features [P][N][256]; f2s: the split form of f2 (launch_split_weights); lvl: the pyramid layout of common.h
-int launch_volume_tile(const float *f1, const float *f2s, int P, int h, int w, float *const lvl[4], hipStream_t s, const PairPtrs *f1p, long long f2_bstride) {
+// a row of raw fp32 features -> its split form through vt_split8 itself (mftx_volume_query_split: the tests compare it with
+// launch_split_weights, value for value)
+__global__ void vt_query_split_kernel(const float *__restrict__ in, uint4 *__restrict__ out, long long n8) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const float k2048 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(0x45000000));
+    if (i >= n8) return;
+    const vt_f32x4 u = *reinterpret_cast<const vt_f32x4 *>(in + i * 8), v = *reinterpret_cast<const vt_f32x4 *>(in + i * 8 + 4);
+    vt_f16x8 hi, lo;
+    vt_split8(u, v, k2048, hi, lo);
+    out[2 * i] = __builtin_bit_cast(uint4, hi);
+    out[2 * i + 1] = __builtin_bit_cast(uint4, lo);
+}
+
+int launch_volume_query_split(const float *in, void *out, long long n, hipStream_t s) {
+    if (n <= 0 || n % 8) return fail(MFTX_E_ARG, "volume_query_split: a positive multiple of 8 floats");
+    if (!aligned16(in) || !aligned16(out)) return fail(MFTX_E_ALIGN, "volume_query_split: operands must be 16-byte aligned");
+    const long long n8 = n / 8;
+    hipLaunchKernelGGL(vt_query_split_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, in, reinterpret_cast<uint4 *>(out), n8);
+    return check_launch("volume_query_split");
+}
+
+// f1: raw fp32 features [P][N][256] (f1_split: their split form); f2s: the split form of f2 (launch_split_weights); lvl: the pyramid layout of common.h
+int launch_volume_tile(const float *f1, const float *f2s, int P, int h, int w, float *const lvl[4], hipStream_t s, const PairPtrs *f1p, long long f2_bstride,
+                       bool f1_split) {
     if (f1p && P > MFTX_MAX_GATHER) return fail(MFTX_E_ARG, "corr_pyramid: at most %d gathered pairs", MFTX_MAX_GATHER);
     const PyramidLayout L = pyramid_layout(h, w);
     VolTileArgs a{};
@@ -369,12 +398,14 @@ int launch_volume_tile(const float *f1, const float *f2s, int P, int h, int w, f
     if (wgs > 0x7fffffffLL) return fail(MFTX_E_ARG, "corr_pyramid: too many workgroups");
     static bool attr_set = false;
     if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(volume_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, VT_LDS) != hipSuccess)
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(volume_tile_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, VT_LDS) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void *>(volume_tile_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, VT_LDS) != hipSuccess)
             return fail(MFTX_E_STATE, "corr_pyramid: cannot reserve %d bytes of LDS", VT_LDS);
         attr_set = true;
     }
     ProfScope prof(PC_CORR_VOLUME, s, 2.0 * a.N * a.N * (double)VT_C * P);
-    hipLaunchKernelGGL(volume_tile_kernel, dim3((unsigned)wgs), dim3(512), VT_LDS, s, a);
+    if (f1_split) hipLaunchKernelGGL(volume_tile_kernel<true>, dim3((unsigned)wgs), dim3(512), VT_LDS, s, a);
+    else hipLaunchKernelGGL(volume_tile_kernel<false>, dim3((unsigned)wgs), dim3(512), VT_LDS, s, a);
     return check_launch("volume_tile");
 }
 

@@ -941,13 +941,36 @@ class RaftEngine:
         return (self.arith == ARITH_SPLIT and not self.ondemand_corr and P <= self.MAX_GATHER and
                 getattr(self, "_tile_volume", 1) != 0 and getattr(self, "_gather", True))
 
+    def prepare_frame(self, fmap, inp, h, w, context=True, split=True):
+        """What a refinement computes from its LEFT frame alone (``mftx_raft_frame_prepare``), on the current stream:
+        -> (ctx, fsplit): ctx = the four context parts (zr1 [N,256], q1 [N,128], zr2 [N,256], q2 [N,128]) or None, fsplit = the split
+        form of fmap [N,256] or None.  ``refine(..., prepared=...)`` takes them in place of recomputing them for every pair.
+        The context parts need ``tile_conv`` pinned (0 or 2) on this handle."""
+        lib = _lib.load()
+        N = h * w
+        dev = self.device
+        ctx = fsplit = scratch = None
+        if context:
+            ctx = tuple(torch.empty(N, c, dtype=torch.float32, device=dev) for c in (256, 128, 256, 128))
+            scratch = torch.empty(lib.mftx_raft_frame_prepare_bytes(h, w), dtype=torch.uint8, device=dev)
+        if split:
+            fsplit = torch.empty(N, 256, dtype=torch.float32, device=dev)
+        cp = [t.data_ptr() for t in ctx] if context else [None] * 4
+        check(lib.mftx_raft_frame_prepare(self._h, h, w, _chk(fmap, "fmap") if split else None, _chk(inp, "inp") if context else None,
+                                          *cp, fsplit.data_ptr() if split else None,
+                                          scratch.data_ptr() if context else None, scratch.numel() if context else 0, _stream()),
+              "mftx_raft_frame_prepare")
+        return ctx, fsplit
+
     def refine(self, fmap1, fmap2, net, inp, h, w, iters, pads=(0, 0, 0, 0), want_flow_lr=False, flow_init=None,
-               packed=None, planar=True):
+               packed=None, planar=True, prepared=None):
         """fmap1/fmap2 [P, h*w, 256], net/inp [P, h*w, 128] pixel-major ->
         flow [P,2,H0,W0], occl [P,1,H0,W0], sigma [P,1,H0,W0] (+ flow_lr [P,h*w,2]).
         flow_init: optional [P, h*w, 2] initial flow at 1/8 resolution (core/raft.py:153-154).
         packed: optional pre-allocated [P,H0,W0,4] that also receives (fx, fy, occl, sigma) per pixel;
-        planar=False (with packed): only the packed result is written, flow = occl = sigma = None."""
+        planar=False (with packed): only the packed result is written, flow = occl = sigma = None.
+        prepared (per-pair map lists only): {"ctx": [the P left frames' context parts, 4 tensors each] | None, "f1s": [the P left
+        frames' split maps] | None, "f2s": the shared right frame's split map | None} from ``prepare_frame``: the same bits."""
         lib = _lib.load()
         gathered = isinstance(fmap1, (list, tuple))      # per-pair maps [h*w, 256] / [h*w, 128] (mftx_raft_refine_gather)
         P = len(fmap1) if gathered else fmap1.shape[0]
@@ -969,6 +992,22 @@ class RaftEngine:
             if not self.can_gather(P) or not (len(fmap2) == len(net) == len(inp) == P):
                 raise MftxError("refine: per-pair map lists need the split arithmetic with the tile-resident volume and P <= 16")
             arrs = [_lib.ptr_array([_chk(t, "map") for t in lst]) for lst in (fmap1, fmap2, net, inp)]
+            if prepared:
+                ctx, f1s, f2s = prepared.get("ctx"), prepared.get("f1s"), prepared.get("f2s")
+                if (ctx is not None and len(ctx) != P) or (f1s is not None and len(f1s) != P):
+                    raise MftxError("refine: prepared parts for every pair, or none")
+                carr = _lib.ptr_array([_chk(t, "context part") for parts in ctx for t in parts]) if ctx is not None else (None, None)
+                sarr = _lib.ptr_array([_chk(t, "split map") for t in f1s]) if f1s is not None else (None, None)
+                check(lib.mftx_raft_refine_gather_ex(self._h, P, h, w, iters, arrs[0][0], arrs[1][0], arrs[2][0], arrs[3][0],
+                                                     carr[0], sarr[0], _chk(f2s, "split map") if f2s is not None else None,
+                                                     _chk(flow_init, "flow_init") if flow_init is not None else None,
+                                                     pl, pr, pt, pb,
+                                                     flow.data_ptr() if planar else None, occl.data_ptr() if planar else None,
+                                                     sigma.data_ptr() if planar else None,
+                                                     _chk(packed, "packed") if packed is not None else None,
+                                                     flow_lr.data_ptr() if want_flow_lr else None,
+                                                     ws.data_ptr(), ws.numel(), _stream()), "mftx_raft_refine_gather_ex")
+                return (flow, occl, sigma, flow_lr) if want_flow_lr else (flow, occl, sigma)
             check(lib.mftx_raft_refine_gather(self._h, P, h, w, iters, arrs[0][0], arrs[1][0], arrs[2][0], arrs[3][0],
                                               _chk(flow_init, "flow_init") if flow_init is not None else None,
                                               pl, pr, pt, pb,
@@ -978,6 +1017,8 @@ class RaftEngine:
                                               flow_lr.data_ptr() if want_flow_lr else None,
                                               ws.data_ptr(), ws.numel(), _stream()), "mftx_raft_refine_gather")
             return (flow, occl, sigma, flow_lr) if want_flow_lr else (flow, occl, sigma)
+        if prepared:
+            raise MftxError("refine: prepared parts go with per-pair map lists")
         check(lib.mftx_raft_refine(self._h, P, h, w, iters, _chk(fmap1, "fmap1"), _chk(fmap2, "fmap2"),
                                    _chk(net, "net"), _chk(inp, "inp"),
                                    _chk(flow_init, "flow_init") if flow_init is not None else None,

@@ -58,11 +58,17 @@ def _shared_stream(device, kind, index=0):
 
 
 class FrameFeatures:
-    __slots__ = ("fmap", "net", "inp", "h", "w", "pads", "shape", "ready")
+    __slots__ = ("fmap", "net", "inp", "h", "w", "pads", "shape", "ready", "ctx", "fsplit")
 
     def __init__(self, fmap, net, inp, h, w, pads, shape, ready=None):
         self.fmap, self.net, self.inp, self.h, self.w, self.pads, self.shape = fmap, net, inp, h, w, pads, shape
         self.ready = ready          # event behind the kernels that wrote the maps (None: ordered by the caller's stream)
+        # what every refinement with this frame on the LEFT would compute from it again (RAFTWrapper._prepare; `ready` covers them):
+        self.ctx = None             # the four context parts of the GRU gate sums, or None: the engine computes them per pair
+        self.fsplit = None          # the split form of fmap, or None: the engine splits it per refinement
+
+    def tensors(self):
+        return [t for t in (self.fmap, self.net, self.inp, self.fsplit) + tuple(self.ctx or ()) if t is not None]
 
 
 class RAFTWrapper:
@@ -135,6 +141,13 @@ class RAFTWrapper:
         # (mftx_tile_conv_fills_chip; an explicit engine_options["tile_conv"] wins).
         self.nominal_pairs = int(getattr(config, "nominal_pairs", 0) or 7)
         self._tile_choice = {}
+        # C.frame_prepare (env MFTX_FRAME_PREPARE overrides; default on): a frame's share of the refinements it will be the LEFT frame
+        # of -- the context features' part of the GRU gate sums, the split form of its feature map -- is computed ONCE, behind its
+        # encoders (_prepare), instead of in every one of its up to seven pairs and in every pair of the template.  Same kernels on
+        # the same values: the same bits.  16.8 MB per cached frame at 512 x 512; switched off per image size where that does not fit.
+        fp = os.environ.get("MFTX_FRAME_PREPARE", "")
+        self._frame_prepare = bool(int(fp)) if fp else bool(getattr(config, "__dict__", {}).get("frame_prepare", True))
+        self._prepare_ok = {}                         # (h, w) -> the prepared parts of the cached frames fit beside the workspaces
         self._frames = {}
         self._staging = {}                            # frame shape -> pinned staging ring (_stage_host_frame)
         # Optional (C.async_encode): encode new frames on a side stream.  The encoders of frame t
@@ -180,6 +193,49 @@ class RAFTWrapper:
         for e in self._all_engines():
             if getattr(e, "_tile_conv", None) != v:
                 e.set_option("tile_conv", v)
+
+    PREPARED_FRAMES = 34           # cached frames the memory check of _prepare counts: the deltas reach 32 back, + template + current
+
+    def _prepare(self, f):
+        """The prepared parts of a frame that will be cached (FrameFeatures.ctx / .fsplit), on the current stream right behind its
+        encoders.  Not for: the fp32 arithmetic, alternate_corr, engines without per-pair map lists (all of them refine from the raw
+        maps as ever); the context parts only where the pinned kernel family is the tile-resident one with the fused GRU pass."""
+        if not self._frame_prepare or f.net is None or not self.engine.can_gather(1) or f.h < 16 or f.w < 16:
+            return
+        opt = self._engine_options
+        if int(opt.get("presplit", 1)) == 0:
+            return
+        self._pin_kernels(f.h, f.w)               # (the family the frame's batches will run: decided for the nominal batch, as there)
+        fits = self._prepare_ok.get((f.h, f.w))
+        if fits is None:
+            per_frame = f.h * f.w * 4096          # 768 floats of context parts + 256 of split map per cell
+            need = self.PREPARED_FRAMES * per_frame
+            ws_bytes = int(ops._lib.load().mftx_raft_workspace_bytes_for(self.engine._h, self.nominal_pairs, f.h, f.w))
+            for k in range(self._fif):            # workspaces the lanes have yet to allocate come first
+                e = self._lanes[k][0] if k < len(self._lanes) else (self.engine if k == 0 else None)
+                have = e._ws.numel() if e is not None and e._ws is not None else 0
+                need += max(0, ws_bytes - have)
+            free, total = torch.cuda.mem_get_info(self.device)
+            cached = torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
+            fits = self._prepare_ok[(f.h, f.w)] = need <= free + cached - total // 10
+            if not fits:
+                logger.warning("frame_prepare: %.1f MB of prepared parts per cached frame of %d x %d cells do not fit beside the "
+                               "workspaces (%.1f GB free): computing them per pair", per_frame / 1e6, f.h, f.w, (free + cached) / 1e9)
+        if not fits:
+            return
+        context = getattr(self.engine, "_tile_conv", 1) == 2 and int(opt.get("fuse_gru", 1)) != 0
+        f.ctx, f.fsplit = self.engine.prepare_frame(f.fmap, f.inp, f.h, f.w, context=context, split=True)
+
+    def _prepared(self, fls, frs, flow_init):
+        """The ``prepared`` argument of RaftEngine.refine for a batch of per-pair map lists, from what its frames carry."""
+        if not self._frame_prepare or flow_init is not None:
+            return None
+        ctx = [f.ctx for f in fls] if all(f.ctx is not None for f in fls) and getattr(self.engine, "_tile_conv", 1) == 2 else None
+        f1s = [f.fsplit for f in fls] if all(f.fsplit is not None for f in fls) else None
+        f2s = frs[0].fsplit if all(f is frs[0] for f in frs) else None
+        if ctx is None and f1s is None and f2s is None:
+            return None
+        return {"ctx": ctx, "f1s": f1s, "f2s": f2s}
 
     def _all_engines(self):
         return list(dict.fromkeys([self.engine] + list(self._engines) + [e for e, _ in self._lanes]))
@@ -405,7 +461,8 @@ class RAFTWrapper:
         return buf, (h, w)
 
     def adopt_halves(self, frame_id, fbuf, cbuf, img_bgr, ready=None):
-        """Install a frame's features from the two ``encode_half`` buffers (produced here or on other ranks)."""
+        """Install a frame's features from the two ``encode_half`` buffers (produced here or on other ranks).
+        (Adopted frames carry no prepared parts: their refinements compute them per pair, as before C.frame_prepare.)"""
         H0, W0 = img_bgr.shape[:2]
         h, w, pads = self._geometry(H0, W0)
         N = h * w
@@ -421,7 +478,8 @@ class RAFTWrapper:
 
     def adopt_packed(self, frame_id, buf, img_bgr, ready=None):
         """Install features produced by ``encode_packed`` (here or on another rank) for ``frame_id``.  ``ready``: an event behind
-        whatever wrote ``buf`` (None: ordered by the stream that is current when the features are used)."""
+        whatever wrote ``buf`` (None: ordered by the stream that is current when the features are used).
+        (Adopted frames carry no prepared parts: their refinements compute them per pair, as before C.frame_prepare.)"""
         H0, W0 = img_bgr.shape[:2]
         h, w, pads = self._geometry(H0, W0)
         N = h * w
@@ -438,7 +496,7 @@ class RAFTWrapper:
         for k in [k for k in self._frames if k not in keep]:
             del self._frames[k]
 
-    def _encode(self, img):
+    def _encode(self, img, prepare=False):
         # Every set of features carries the event behind its encoders, whatever frames_in_flight says right now: features live in the
         # cache for up to 32 frames, and a lane that meets one WITHOUT an event must wait for the caller's whole stream -- i.e. for the
         # previous frame's selection -- which silently serialises the lanes (round 5: a plugin whose frames_in_flight was lowered
@@ -451,6 +509,8 @@ class RAFTWrapper:
             cur = torch.cuda.current_stream()
             self._encode_begin(cur)
             f = self.encode(img)
+            if prepare:
+                self._prepare(f)
             f.ready = cur.record_event()
             self._encode_end(f.ready, cur)
             return f
@@ -463,18 +523,21 @@ class RAFTWrapper:
             # prefetch: encode_packed / encode_half) run on the encode stream: this encode waits for those, and they for it.
             self._encode_begin(main)
             f = self.encode(img)
+            if prepare:
+                self._prepare(f)
             f.ready = main.record_event()
             self._encode_end(f.ready, main)
             return f
         self._encode_begin(self._enc_stream)
         with torch.cuda.stream(self._enc_stream):
             f = self.encode(img)
+            if prepare:
+                self._prepare(f)
             f.ready = self._enc_stream.record_event()
         self._encode_end(f.ready, self._enc_stream)
         main.wait_stream(self._enc_stream)
-        for t in (f.fmap, f.net, f.inp):          # allocated on the side stream, consumed on `main`
-            if t is not None:
-                t.record_stream(main)
+        for t in f.tensors():                     # allocated on the side stream, consumed on `main`
+            t.record_stream(main)
         return f
 
     def _encode_begin(self, stream):
@@ -490,7 +553,7 @@ class RAFTWrapper:
             return self._encode(img)
         f = self._frames.get(key)
         if f is None or f.shape != img.shape[:2]:
-            f = self._encode(img)
+            f = self._encode(img, prepare=True)   # (a cached frame will be the left frame of later pairs)
             self._frames[key] = f
         return f
 
@@ -526,11 +589,13 @@ class RAFTWrapper:
         packed = None
         H0, W0 = ref.shape
         want_planar = planar or packed_out is None or packed_out is False
+        self._pin_kernels(ref.h, ref.w)
+        prepared = self._prepared(fls, frs, flow_init) if gather else None
         if (self._fif > 1 and gather and flow_init is None and not self._check_finite
                 and (packed_out is None or isinstance(packed_out, bool))):
             # (one frame's batch as two halves on the two lanes -- for the caller that synchronises per frame -- was measured in
             # round 6: the pipelined rate falls 188 -> 171 frames/s and the per-frame-synchronised rate does not move, 150 -> 150.)
-            return self._refine_on_lane(fls, frs, fmap1, fmap2, net, inp, ref, iters, bool(packed_out), want_planar)
+            return self._refine_on_lane(fls, frs, fmap1, fmap2, net, inp, ref, iters, bool(packed_out), want_planar, prepared)
         if packed_out is not None and packed_out is not False:
             packed = packed_out if isinstance(packed_out, torch.Tensor) else \
                 torch.empty(P, H0, W0, 4, dtype=torch.float32, device=self.device)
@@ -543,7 +608,7 @@ class RAFTWrapper:
             flow, occl, sigma = self._refine_split(fmap1, fmap2, net, inp, ref, iters, packed, want_planar)
         else:
             flow, occl, sigma = self.engine.refine(fmap1, fmap2, net, inp, ref.h, ref.w, iters, pads=ref.pads,
-                                                   flow_init=flow_init, packed=packed, planar=want_planar)
+                                                   flow_init=flow_init, packed=packed, planar=want_planar, prepared=prepared)
         if self._check_finite:
             bad = sum(ops.count_not_below(t.reshape(-1), float("inf")) for t in (packed, flow, occl, sigma) if t is not None)
             if bad:
@@ -557,7 +622,7 @@ class RAFTWrapper:
             return [(flow[i], occl[i], sigma[i], packed[i]) for i in range(P)]
         return [(flow[i], occl[i], sigma[i]) for i in range(P)]
 
-    def _refine_on_lane(self, fls, frs, fmap1, fmap2, net, inp, geom, iters, want_packed, planar):
+    def _refine_on_lane(self, fls, frs, fmap1, fmap2, net, inp, geom, iters, want_packed, planar, prepared=None):
         """One batch on the next lane of C.frames_in_flight (see __init__): the lane's stream waits for the frames' features
         only, the caller's stream for the lane -- whatever else is queued on the caller's stream (the previous frame's chaining
         and selection, result copies) does not hold the batch back."""
@@ -576,14 +641,13 @@ class RAFTWrapper:
                 st.wait_event(f.ready)
             else:
                 st.wait_stream(main)                  # features without an event: ordered by the caller's stream
-            for t in (f.fmap, f.net, f.inp):
-                if t is not None:
-                    t.record_stream(st)
+            for t in f.tensors():
+                t.record_stream(st)
         with torch.cuda.stream(st):
             # (outputs come from the LANE's pool: a block the caller's stream freed a moment ago may still be read there)
             packed = torch.empty(P, H0, W0, 4, dtype=torch.float32, device=self.device) if want_packed else None
             flow, occl, sigma = eng.refine(fmap1, fmap2, net, inp, geom.h, geom.w, iters, pads=geom.pads,
-                                           flow_init=None, packed=packed, planar=planar)
+                                           flow_init=None, packed=packed, planar=planar, prepared=prepared)
             done = st.record_event()
         main.wait_event(done)
         self._ahead.append(done)
