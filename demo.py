@@ -2,12 +2,14 @@
 """Track every pixel of a video with MFT and write the point / edit overlays -- the reference's ``demo.py`` on
 the MI355X engine.
 
-    python demo.py --video <dir of PNG frames | frames.npy> [--edit edit.png] [--out demo_out/] [--synthetic]
+    python demo.py --video <dir of PNG frames | frames.npy> [--edit edit.png] [--out demo_out/] [--synthetic] [--gpu-overlays]
 
 Differences forced by the environment: no OpenCV here, so the input is a directory of PNG frames or a ``.npy``
 frame array (video containers work when cv2 is importable) and the overlays are written as numbered PNGs instead of
 an mp4; ``--synthetic`` tracks the seeded synthetic video with seeded stand-in weights (no checkpoint ships with
-this build).  Frames go to the GPU through a pinned upload ring (``mft_amd/video.py:FrameRing``).
+this build).  Frames go to the GPU through a pinned upload ring (``mft_amd/video.py:FrameRing``).  With ``--gpu-overlays``
+both overlays are rendered on the GPU inside the tracking loop (``mft_amd/vis.py:DeviceOverlay``) and written as they
+arrive: no dense result is downloaded or kept.
 """
 import argparse
 import logging
@@ -38,6 +40,7 @@ def parse_arguments():
     ap.add_argument('--grid_spacing', type=int, default=30)
     ap.add_argument('--synthetic', type=int, default=0, metavar='N', help='track N frames of the seeded synthetic video')
     ap.add_argument('--synthetic_weights_seed', type=int, default=None, help='run on seeded stand-in weights')
+    ap.add_argument('--gpu-overlays', action='store_true', help='render the overlays on the GPU while tracking; dense results stay on the device')
     return ap.parse_args()
 
 
@@ -59,6 +62,8 @@ def run(args):
         frames = list(vio.get_video_frames(args.video))
         name = args.video.stem
     logger.info("tracking %d frames", len(frames))
+    if args.gpu_overlays:
+        return run_gpu_overlays(args, tracker, frames, name)
     from mft_amd.results import FlowOUTrackingResult
     results, host_results, queries = [], [], None
     drain = vio.ResultDrain()
@@ -84,6 +89,40 @@ def run(args):
         vio.imwrite_bgr(args.out / f"{name}_points" / f"{i:05d}.png", vis.draw_dots(frame, coords, occlusions))
         if edit is not None:
             vio.imwrite_bgr(args.out / f"{name}_edit" / f"{i:05d}.png", vis.draw_edit(frame, result, edit))
+    logger.info("wrote %s", args.out)
+    return 0
+
+
+def run_gpu_overlays(args, tracker, frames, name):
+    """The same loop with the overlays rendered on the device: per frame the tracker's result feeds ``DeviceOverlay.render``
+    on the tracking stream, and the finished uint8 frames are written as their downloads land."""
+    edit = vio.imread_unchanged(args.edit) if args.edit.exists() else None
+    up = [torch.cuda.current_stream()]
+    if getattr(tracker.flower, "_enc_stream", None) is not None:
+        up.append(tracker.flower._enc_stream)
+    written = 0
+
+    def write(done):
+        nonlocal written
+        for points, edited in done:
+            vio.imwrite_bgr(args.out / f"{name}_points" / f"{written:05d}.png", points)
+            if edited is not None:
+                vio.imwrite_bgr(args.out / f"{name}_edit" / f"{written:05d}.png", edited)
+            written += 1
+
+    overlay = None
+    for i, dev_frame in enumerate(vio.FrameRing(frames, streams=up)):
+        if i == 0:
+            meta = tracker.init(dev_frame)
+            meta.result = meta.result.cuda()
+            H, W = frames[0].shape[:2]
+            overlay = vis.DeviceOverlay(edit, vis.get_queries((H, W), args.grid_spacing), H, W)
+        else:
+            meta = tracker.track(dev_frame)
+        overlay.render(dev_frame, meta.result)
+        write(overlay.download())
+    if overlay is not None:
+        write(overlay.download(wait=True))
     logger.info("wrote %s", args.out)
     return 0
 

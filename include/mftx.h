@@ -498,6 +498,50 @@ int mftx_sample_points(int T, const float *const *flow, const float *const *occl
                        int H, int W, int N, const int *tmpl, const float *xy,
                        float *table, long long row_stride, int column, void *stream);
 
+/* ---- forward splat: FlowOUTrackingResult.warp_forward (MFT/results.py:190-248 with MFT/utils/interpolation.py:234-309),
+ * bitwise reproducible.  Every kept template pixel (column x, row y; mask [H][W] bytes, non-zero = kept, or NULL) spreads
+ * its C values over the four pixels around dst = g + flow (fp32):
+ *   x0 = floor(x), x1 = x0 + 1, likewise y; THEN x is clamped to [0, W-1], y to [0, H-1], and so are x0, x1, y0, y1;
+ *   wx0 = x1 - x, wx1 = x - x0, wy0 = y1 - y, wy1 = y - y0; the four fp32 products go
+ *   wx0*wy0 -> (y0, x0), wx0*wy1 -> (y1, x0), wx1*wy0 -> (y0, x1), wx1*wy1 -> (y1, x1).
+ * A pixel whose destination is not finite contributes nothing.  The sums are 64-bit integers in fixed point:
+ *   q_w = rint(w * 2^S) (half-even; a corner with q_w == 0 is dropped);
+ *   v_q = v for uint8 values (V = 0), rint((double)v * 2^V) for float32 values (a non-finite value counts as 0);
+ *   acc[c][p] += v_q[c] * q_w, cnt[p] += q_w, by 64-bit atomic adds without return.
+ * Integer addition is associative: the result does not depend on the order the adds arrive in.  acc: [C + 1][H][W] int64
+ * (plane C = cnt), ZERO on entry.  The caller chooses S and V such that 4 H W * max|v_q| * 2^S <= 2^62 (mft_amd/ops.py:
+ * splat_plan); accepted here: S in 16..24, V = 0 (uint8) or 12..23 (float32).  img: [H][W][C]. */
+#define MFTX_SPLAT_F32 0
+#define MFTX_SPLAT_U8 1
+int mftx_splat_forward(const float *flow, const void *img, int img_dtype, const uint8_t *mask, int C, int H, int W,
+                       int S, int V, long long *acc, void *stream);
+
+/* out [H][W][C] = (float)((double)acc[c] / ((double)cnt * 2^V)) where cnt > 0, `fill` elsewhere (0, or the border value).
+ * clear != 0: every accumulator word that was not zero is zeroed behind the read, so a per-frame loop needs no memset. */
+int mftx_splat_resolve(long long *acc, int C, int H, int W, int V, float fill, int clear, float *out, void *stream);
+
+/* ---- demo overlays (demo.py:116-146) ---------------------------------------------------------------------------------
+ * The first-frame edit ([H][W][4] uint8: B, G, R, A) carried along the flow onto the gray current frame ([H][W][3] uint8
+ * BGR) -> out [H][W][3] uint8.  Two launches:
+ *  1. the splat above of the integer channels (b a, g a, r a, a) -- |v| < 2^16, V = 0 -- for template pixels with
+ *     occlusion < 0.5 (a NaN is masked out) and a > 0;
+ *  2. resolve + blend + clear:  colour_c = (float)((double)acc_c / ((double)cnt * 255.0)) clipped to [0, 255] and truncated;
+ *     alpha = (float)((double)acc_a / (double)cnt) / alpha_div;  gray = (1868 b + 9617 g + 4899 r + 8192) >> 14;
+ *     out_c = trunc(clip(colour_c + gray * (1 - alpha), 0, 255)) in fp32; where nothing arrived colour = alpha = 0.
+ * alpha_div: 255, or 1 if every non-zero alpha of the edit equals 1 (the reference's blend only rescales an alpha map
+ * whose maximum exceeds 1).  acc: [5][H][W] int64, zero on entry and zero again on exit.  For measurements the launches can
+ * be issued one by one: out == NULL is launch 1 alone, edit == NULL launch 2 alone (of what acc holds). */
+int mftx_overlay_edit(const float *flow, const float *occl, const uint8_t *edit, const uint8_t *frame, int H, int W,
+                      int S, float alpha_div, long long *acc, uint8_t *out, void *stream);
+
+/* A filled dot of one colour at every visible tracked point: out = frame ([H][W][3] uint8; copied first unless
+ * out == frame), then for row i of the table (x, y, occlusion, sigma -- what the point read-out above writes; row_stride in
+ * floats), skipped if occlusion > 0.5 or a coordinate is not finite, in fp64:  cx = rint(x), cy = rint(y) (half-even);
+ * every (dx, dy) in [-ceil(radius), ceil(radius)]^2 with (dx + cx - x)^2 + (dy + cy - y)^2 <= (radius + 0.5)^2 and
+ * (cx + dx, cy + dy) inside the frame is set to (b, g, r).  One wave per point. */
+int mftx_overlay_dots(const uint8_t *frame, uint8_t *out, int H, int W, const float *table, long long row_stride,
+                      int N, double radius, int b, int g, int r, void *stream);
+
 /* ---- 8f-2: flow-cache codec (".flowouX16" entries) -----------------------------
  * Replaces compress_channel / decompress_channel of write_flowou_X16 / read_flowou_X16
  * (MFT/utils/io.py:495-512, 548-551): per-channel min/max, uint16 quantisation with

@@ -10,6 +10,8 @@ RuntimeError).
 from __future__ import annotations
 
 import ctypes as C
+import math
+from typing import NamedTuple
 
 import torch
 
@@ -741,6 +743,135 @@ def sample_points(results, tmpl, xy, table, column):
                                  _chk(xy, "xy"), _chk(table, "table"), 4 * frames, int(column), _stream()),
           "mftx_sample_points")
     return table
+
+
+# ---------------------------------------------------------------------------
+# forward splat + demo overlays (csrc/splat.hip): 64-bit integer fixed point, bitwise reproducible
+# ---------------------------------------------------------------------------
+
+class SplatPlan(NamedTuple):
+    S: int            # weight bits: q_w = rint(w * 2^S)
+    V: int            # value bits: v_q = rint(v * 2^V); 0 for integer values
+    L: int            # ceil(log2(4 H W)): no destination receives more than 2^L contributions
+    native: bool      # False: too few bits left for the integer path (S < 16, or V < 12 for float values)
+
+
+def splat_plan(H: int, W: int, k: int, floating: bool) -> SplatPlan:
+    """Fixed-point formats of a forward splat of values |v| < 2^k on an H x W frame (pure host arithmetic).
+
+    Weights are at most 1 and at most 4 H W <= 2^L contributions reach one destination, so every accumulator word stays
+    within 2^(L + k + V + S) <= 2^62: overflow is excluded by construction, not by testing.  Integer values keep V = 0 and
+    take S = min(24, 62 - L - k); float values take S = 24 (every bit of an fp32 weight product that matters) and
+    V = min(23, 62 - L - k - 24).  ``native`` is False where that leaves S < 16, or V < 12 for float values: the native
+    path then refuses and the caller uses ``FlowOUTrackingResult.warp_forward``."""
+    H, W, k = int(H), int(W), int(k)
+    if H < 1 or W < 1 or k < 0:
+        raise ValueError("splat_plan: need H, W >= 1 and k >= 0")
+    L = (4 * H * W - 1).bit_length()
+    if floating:
+        S, V = 24, min(23, 62 - L - k - 24)
+        return SplatPlan(S, V, L, V >= 12)
+    S = min(24, 62 - L - k)
+    return SplatPlan(S, 0, L, S >= 16)
+
+
+def value_bits(bound: float) -> int:
+    """The smallest k >= 0 with bound < 2^k."""
+    bound = float(bound)
+    if not math.isfinite(bound) or bound < 0:
+        raise MftxError("splat: the value bound must be finite and non-negative")
+    return max(0, math.frexp(bound)[1])           # bound = m 2^e with 0.5 <= m < 1
+
+
+def splat_accumulator(C: int, H: int, W: int, device) -> torch.Tensor:
+    """A zeroed accumulator [C + 1, H, W] int64 (plane C: the weight sums)."""
+    return torch.zeros(C + 1, H, W, dtype=torch.int64, device=device)
+
+
+def splat_forward(flow, img, value_bound, mask=None, border=None, acc=None):
+    """Forward splat of ``img`` [H, W, C] (float32 or uint8, device) along ``flow`` [2, H, W] -> float32 [H, W, C]
+    (``mftx_splat_forward`` + ``mftx_splat_resolve``): what ``FlowOUTrackingResult.warp_forward`` computes, with the sums in
+    64-bit integers.  ``value_bound``: max |img| (float32 values beyond it can overflow the accumulator; uint8 needs none);
+    mask: [H, W] bool / uint8 of kept template pixels; pixels nothing reached are 0 or ``border``.  ``acc``: a zeroed
+    ``splat_accumulator(C, H, W)`` to reuse -- the resolve clears it behind itself.  No host synchronisation."""
+    lib = _lib.load()
+    if img.dim() != 3:
+        raise MftxError("splat_forward: img must be [H, W, C]")
+    H, W, Cc = (int(s) for s in img.shape)
+    if tuple(flow.shape) != (2, H, W):
+        raise MftxError("splat_forward: flow must be [2,H,W] matching img")
+    if img.dtype == torch.uint8:
+        dtype, plan = 1, splat_plan(H, W, 8, False)
+    else:
+        dtype, plan = 0, splat_plan(H, W, value_bits(value_bound), True)
+    if not plan.native:
+        raise MftxError(f"splat_forward: {H} x {W} with this value range leaves S = {plan.S}, V = {plan.V} bits "
+                        "for the integer accumulator (needs S >= 16 and V >= 12 for float values): use warp_forward")
+    mp = None
+    if mask is not None:
+        if tuple(mask.shape) != (H, W) or mask.dtype not in (torch.bool, torch.uint8):
+            raise MftxError("splat_forward: mask must be [H,W] bool or uint8")
+        mp = _chk(mask, "mask", mask.dtype)
+    if acc is None:
+        acc = splat_accumulator(Cc, H, W, img.device)
+    elif tuple(acc.shape) != (Cc + 1, H, W):
+        raise MftxError("splat_forward: acc must be [C+1,H,W]")
+    out = torch.empty(H, W, Cc, dtype=torch.float32, device=img.device)
+    check(lib.mftx_splat_forward(_chk(flow, "flow"), _chk(img, "img", img.dtype), dtype, mp, Cc, H, W, plan.S, plan.V,
+                                 _chk(acc, "acc", torch.int64), _stream()), "mftx_splat_forward")
+    check(lib.mftx_splat_resolve(acc.data_ptr(), Cc, H, W, plan.V, 0.0 if border is None else float(border), 1,
+                                 out.data_ptr(), _stream()), "mftx_splat_resolve")
+    return out
+
+
+def edit_alpha_divisor(edit) -> float:
+    """``vis.blend_with_alpha_premult`` rescales the warped alpha only if its maximum exceeds 1.0001: the divisor is 255
+    unless every non-zero alpha of the edit equals 1.  Decided once, on the host, from the edit (numpy [H, W, 4] uint8)."""
+    return 255.0 if int(edit[..., 3].max(initial=0)) > 1 else 1.0
+
+
+def overlay_edit(flow, occl, edit, frame, acc, alpha_div=255.0, out=None):
+    """The BGRA edit [H, W, 4] uint8 splatted along the flow for visible template pixels and blended onto the gray frame
+    [H, W, 3] uint8 -> [H, W, 3] uint8 (``mftx_overlay_edit``: ``vis.draw_edit``).  ``acc``: a zeroed
+    ``splat_accumulator(4, H, W)``, zero again afterwards."""
+    lib = _lib.load()
+    H, W = int(frame.shape[0]), int(frame.shape[1])
+    if tuple(frame.shape) != (H, W, 3) or tuple(edit.shape) != (H, W, 4):
+        raise MftxError("overlay_edit: frame must be [H,W,3] and edit [H,W,4]")
+    if tuple(flow.shape) != (2, H, W) or occl.numel() != H * W or tuple(acc.shape) != (5, H, W):
+        raise MftxError("overlay_edit: flow must be [2,H,W], occlusion [1,H,W], acc [5,H,W]")
+    plan = splat_plan(H, W, 16, False)
+    if not plan.native:
+        raise MftxError(f"overlay_edit: {H} x {W} leaves S = {plan.S} weight bits (needs 16): use vis.draw_edit")
+    if out is None:
+        out = torch.empty(H, W, 3, dtype=torch.uint8, device=frame.device)
+    elif tuple(out.shape) != (H, W, 3):
+        raise MftxError("overlay_edit: out must be [H,W,3]")
+    check(lib.mftx_overlay_edit(_chk(flow, "flow"), _chk(occl, "occlusion"), _chk(edit, "edit", torch.uint8),
+                                _chk(frame, "frame", torch.uint8), H, W, plan.S, float(alpha_div),
+                                _chk(acc, "acc", torch.int64), _chk(out, "out", torch.uint8), _stream()), "mftx_overlay_edit")
+    return out
+
+
+def overlay_dots(frame, table, radius=3, color=(0, 0, 255), out=None):
+    """A dot of ``color`` (BGR) at every visible point of ``table`` [N, 4] float32 = (x, y, occlusion, sigma), as
+    ``sample_points`` writes it, on a copy of ``frame`` [H, W, 3] uint8 (``mftx_overlay_dots``: ``vis.draw_dots``).
+    ``out=frame`` draws in place."""
+    lib = _lib.load()
+    H, W = int(frame.shape[0]), int(frame.shape[1])
+    if tuple(frame.shape) != (H, W, 3):
+        raise MftxError("overlay_dots: frame must be [H,W,3]")
+    if table.dim() != 2 or int(table.shape[1]) != 4:
+        raise MftxError("overlay_dots: the table must be [N, 4]")
+    if out is None:
+        out = torch.empty_like(frame)
+    elif tuple(out.shape) != (H, W, 3):
+        raise MftxError("overlay_dots: out must be [H,W,3]")
+    N = int(table.shape[0])
+    check(lib.mftx_overlay_dots(_chk(frame, "frame", torch.uint8), _chk(out, "out", torch.uint8), H, W,
+                                _chk(table, "table") if N else None, 4, N, float(radius), int(color[0]), int(color[1]),
+                                int(color[2]), _stream()), "mftx_overlay_dots")
+    return out
 
 
 _quant_ws = {}

@@ -200,6 +200,28 @@ class FlowOUTrackingResult(object):
             out[~hit] = border
         return out.reshape(H, W, *extra).cpu().numpy()
 
+    def warp_forward_device(self, img, mask=None, border=None, value_bound=None):
+        """``warp_forward`` on libmftx's splat kernels (``ops.splat_forward``): same corners and fp32 weights, the sums in
+        64-bit integer fixed point, so the result is bitwise reproducible.  ``img`` (H, W, ...) float or uint8; returns a
+        DEVICE float32 tensor shaped like ``img``.  ``value_bound``: an upper bound of |img| (it sizes the fixed point; larger
+        values may overflow); given, nothing here synchronises -- without it max |img| is read once.  Raises ``MftxError``
+        where the frame size and value range leave too few bits (``ops.splat_plan``): use ``warp_forward`` there."""
+        dev = self.flow.device
+        H, W = self.H, self.W
+        assert tuple(img.shape[:2]) == (H, W)
+        vals = torch.as_tensor(np.asarray(img) if not isinstance(img, torch.Tensor) else img).to(dev)
+        shape = vals.shape
+        if vals.dtype != torch.uint8:
+            vals = vals.to(torch.float32)
+            if value_bound is None:
+                value_bound = float(vals.abs().max()) if vals.numel() else 0.0
+        vals = vals.reshape(H, W, -1).contiguous()
+        if mask is not None:
+            mask = torch.as_tensor(np.asarray(mask) if not isinstance(mask, torch.Tensor) else mask).to(dev)
+            mask = (mask if mask.dtype in (torch.bool, torch.uint8) else mask.bool()).reshape(H, W).contiguous()
+        out = ops.splat_forward(self.flow.to(torch.float32).contiguous(), vals, value_bound, mask=mask, border=border)
+        return out.reshape(shape)
+
     def invalid_mask(self):
         """(H, W) bool, True where the flow points outside the image
         (MFT/results.py:250-265)."""
