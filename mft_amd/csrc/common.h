@@ -148,7 +148,7 @@ struct PairPtrs { const float *p[MFTX_MAX_GATHER]; };
 // f1_split: the query features (f1 / f1p) are in split form already (mftx_raft_frame_prepare)
 int launch_volume_tile(const float *f1, const float *f2s, int P, int h, int w, float *const lvl[4], hipStream_t s,
                        const PairPtrs *f1p = nullptr, long long f2_bstride = -1, bool f1_split = false);
-int launch_volume_query_split(const float *in, void *out, long long n_floats, hipStream_t s);    // vt_split8 over a buffer (tests)
+int launch_volume_query_split(const float *in, void *out, long long n_floats, hipStream_t s);    // device_prims.h: split8 over a buffer (tests)
 int launch_corr_lookup(const float *const lvl[4], const float *coords, int P, int h, int w,
                        float *out, int ld_out, hipStream_t s);
 // lookup fused into convc1 (csrc/lookup_convc1.hip): out = relu(convc1(lookup(coords)) + bias), [M][ld_out], fp32 or split form

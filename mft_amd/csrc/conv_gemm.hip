@@ -33,15 +33,11 @@
 //     group's MFMAs, so LDS latency and barrier skew hide under matrix work.
 #include "common.h"
 #include "profile.h"
+#include "device_prims.h"
 #include <cstdlib>
 #include <type_traits>
 
 namespace mftx {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // Arithmetic of the matrix products (template parameter AR):
 //   AR_F32  : v_mfma_f32_32x32x2_f32, exact fp32 products, 157 TF peak;
@@ -67,43 +63,6 @@ __device__ unsigned long long mftx_dbg[16];
 #else
 #define STAMP(i)
 #endif
-
-// hi / lo halves of 8 consecutive k of an activation row, 2.5 instructions per value: v_cvt_pk_f16_f32 for two
-// (round to nearest), the exact residual as one mixed-precision fma each (x - hi, hi read as fp16), and the scaled
-// low half as v_fma_mixlo/mixhi_f16 (r * 2048 rounded to fp16 into one half of the destination).  Written as one
-// assembly block: the compiler's own selection for this arithmetic takes 4 instructions per value, and does not
-// know the mixed forms.  The block ends with the two wait states a VALU result needs before an MFMA reads it
-// (the hazard recognizer does not see into inline assembly).
-__device__ __forceinline__ void split8(const f32x4 &u, const f32x4 &v, float k2048, f16x8 &hi, f16x8 &lo) {
-    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-    float r0, r1, r2, r3, r4, r5, r6, r7;
-    asm("v_cvt_pk_f16_f32 %0, %16, %17\n\t"
-        "v_cvt_pk_f16_f32 %1, %18, %19\n\t"
-        "v_cvt_pk_f16_f32 %2, %20, %21\n\t"
-        "v_cvt_pk_f16_f32 %3, %22, %23\n\t"
-        "v_fma_mix_f32 %8, %0, -1.0, %16 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %9, %0, -1.0, %17 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %10, %1, -1.0, %18 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %11, %1, -1.0, %19 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %12, %2, -1.0, %20 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %13, %2, -1.0, %21 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %14, %3, -1.0, %22 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %15, %3, -1.0, %23 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixlo_f16 %4, %8, %24, 0\n\t"
-        "v_fma_mixlo_f16 %5, %10, %24, 0\n\t"
-        "v_fma_mixlo_f16 %6, %12, %24, 0\n\t"
-        "v_fma_mixlo_f16 %7, %14, %24, 0\n\t"
-        "v_fma_mixhi_f16 %4, %9, %24, 0\n\t"
-        "v_fma_mixhi_f16 %5, %11, %24, 0\n\t"
-        "v_fma_mixhi_f16 %6, %13, %24, 0\n\t"
-        "v_fma_mixhi_f16 %7, %15, %24, 0\n\t"
-        "s_nop 1"
-        : "=&v"(h0), "=&v"(h1), "=&v"(h2), "=&v"(h3), "=&v"(l0), "=&v"(l1), "=&v"(l2), "=&v"(l3),
-          "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5), "=&v"(r6), "=&v"(r7)
-        : "v"(u[0]), "v"(u[1]), "v"(u[2]), "v"(u[3]), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "s"(k2048));
-    hi = __builtin_bit_cast(f16x8, u32x4{h0, h1, h2, h3});
-    lo = __builtin_bit_cast(f16x8, u32x4{l0, l1, l2, l3});
-}
 
 constexpr int BK = 32;
 constexpr int LDK = BK;                  // LDS row (floats): unpadded, XOR-swizzled 16-byte chunks
@@ -139,19 +98,6 @@ struct ConvArgs {
     float *lvl1, *lvl2, *lvl3;
     long long s0, s1, s2, s3;                   // floats per query cell, per level
 };
-
-// The same for two values, as the piece that is slotted between two MFMAs of the K loop (5 instructions: they issue
-// in the shadow of one 32-cycle MFMA).  No trailing wait states: the halves are consumed at least two MFMAs later.
-__device__ __forceinline__ void split_pair(float x0, float x1, float k2048, unsigned &h, unsigned &l) {
-    float r0, r1;
-    asm("v_cvt_pk_f16_f32 %0, %4, %5\n\t"
-        "v_fma_mix_f32 %2, %0, -1.0, %4 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %3, %0, -1.0, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixlo_f16 %1, %2, %6, 0\n\t"
-        "v_fma_mixhi_f16 %1, %3, %6, 0"
-        : "=&v"(h), "=&v"(l), "=&v"(r0), "=&v"(r1)
-        : "v"(x0), "v"(x1), "s"(k2048));
-}
 
 // Four consecutive channels nb .. nb + 3 (nb % 4 == 0) of a SPLIT-format row: their fp16 high halves are 8 bytes at
 // group (nb >> 3), half ((nb >> 2) & 1); the low halves 16 bytes further (common.h: split_row_offset)
@@ -190,20 +136,6 @@ __device__ __forceinline__ void store_split4(float *row, int nb, const f32x4 &o,
 #define MFTX_SABL 0
 #endif
 
-// Gate non-linearities of the GRU epilogues on the hardware exponential (v_exp_f32, ~1 ulp) and
-// reciprocal: 16 values per lane and tile, where libm's expf / tanhf cost ~7 % of the q-gate kernel.
-// Absolute error < 2e-7 on outputs in (-1, 1) -- four orders below the parity tolerance; the same
-// code runs for every tile shape and batch, so results stay independent of both.
-__device__ __forceinline__ float fast_sigmoid(float s) { return __frcp_rn(1.f + __expf(-s)); }
-__device__ __forceinline__ float fast_tanh(float s) {
-    const float t = __expf(-2.f * fabsf(s));            // in (0, 1]: no overflow
-    return copysignf((1.f - t) * __frcp_rn(1.f + t), s);
-}
-
-// h <- (1 - z) h + z q, with the contraction spelled out: the scalar and the vectorised epilogues (and every tile shape) must
-// round alike, whatever the compiler would fuse in each
-__device__ __forceinline__ float gru_blend(float z, float h, float q) { return __fmaf_rn(z, q, __fmul_rn(__fsub_rn(1.f, z), h)); }
-
 __device__ __forceinline__ float act_fn(float v, int act) {
     switch (act) {
         case 1: return relu_keep_nan(v);
@@ -211,33 +143,6 @@ __device__ __forceinline__ float act_fn(float v, int act) {
         case 3: return tanhf(v);
         default: return v;
     }
-}
-
-__device__ __forceinline__ f32x4 buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
-}
-
-// 16 bytes per lane straight into LDS: the wave's 64 lanes land lane-linear at `dst` (wave-uniform);
-// an out-of-range offset stores zeros.
-// soff: wave-uniform byte offset added to the address (not part of the range check, which is on voff alone)
-__device__ __forceinline__ void buf_load_lds(__amdgpu_buffer_rsrc_t r, float *dst, unsigned voff, unsigned soff = 0) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)dst, 16, voff, soff, 0, 0);
-}
-
-// s_barrier with compiler fences on both sides (the intrinsic alone does not order LDS accesses)
-__device__ __forceinline__ void block_barrier() {
-    // s_waitcnt lgkmcnt(0): gfx950 has back-off barriers, so the compiler inserts NO wait in front of s_barrier and the builtin is no
-    // fence -- without this a wave's last ds_write may still sit in the LDS queue when another wave reads the slot behind the
-    // barrier (found in round 5 with tools/race_kernels.py: harmless with the GPU to itself, wrong values under contention).
-    // LDS only: global prefetches and LDS-DMA loads (vmcnt) stay in flight, their consumers count them themselves.
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {   // counted wait: leaves N LDS-DMA loads in flight
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // Waves per SIMD the register allocator must leave room for (second __launch_bounds__ argument):
@@ -259,10 +164,6 @@ constexpr int min_waves_split(int wave_tiles, int waves, int mt = 32) { return m
 //            query, stored as a full 128-byte line, and kept in LDS for
 //   level 2 (4 x 2 per super-block) and level 3 (2 x 1), formed the same way from the level below --
 // bit-identical to avg_pool2d applied level by level (core/corr.py:26-28); no second pass over the volume.
-__device__ __forceinline__ float pool4(const float2 top, const float2 bot) {
-    return (((top.x + top.y) + bot.x) + bot.y) * 0.25f;
-}
-
 __device__ __forceinline__ void volume_epilogue(const ConvArgs &p, const f32x16 (&acc)[4], float *st, int lane,
                                                 int q0, int sb, int bz) {
     const int Nq = p.M;                                       // query cells per pair
@@ -303,7 +204,7 @@ __device__ __forceinline__ void volume_epilogue(const ConvArgs &p, const f32x16 
     for (int t = 0; t < 16; ++t) {
         const int e = t * 64 + lane, row = e >> 5, pos = e & 31, y1 = pos >> 3, x1 = pos & 7;
         const float *s = st + row * 128 + ((y1 >> 1) * 2 + (x1 >> 2)) * 32 + (y1 & 1) * 16 + (x1 & 3) * 2;
-        l1[t] = pool4(*reinterpret_cast<const float2 *>(s), *reinterpret_cast<const float2 *>(s + 8));
+        l1[t] = pool4(s[0], s[1], s[8], s[9]);
     }
 #pragma unroll
     for (int t = 0; t < 16; ++t) {
@@ -322,7 +223,7 @@ __device__ __forceinline__ void volume_epilogue(const ConvArgs &p, const f32x16 
     for (int t = 0; t < 4; ++t) {
         const int e = t * 64 + lane, row = e >> 3, y2 = (e >> 2) & 1, x2 = e & 3;
         const float *s = st + row * 32 + y2 * 16 + x2 * 2;
-        l2[t] = pool4(*reinterpret_cast<const float2 *>(s), *reinterpret_cast<const float2 *>(s + 8));
+        l2[t] = pool4(s[0], s[1], s[8], s[9]);
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -335,7 +236,7 @@ __device__ __forceinline__ void volume_epilogue(const ConvArgs &p, const f32x16 
     {
         const int row = lane >> 1, x3l = lane & 1;
         const float *s = st + 1024 + row * 8 + x3l * 2;
-        const float v = pool4(*reinterpret_cast<const float2 *>(s), *reinterpret_cast<const float2 *>(s + 4));
+        const float v = pool4(s[0], s[1], s[4], s[5]);
         const int q = q0 + row, x3 = 2 * sbx + x3l;
         if (q < Nq && sby < h3 && x3 < w3) p.lvl3[(qbase + q) * p.s3 + (long long)sby * w3 + x3] = v;
     }
@@ -483,7 +384,7 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs &p, int vt0) {
     const int n0 = (VOL_M_INNER ? r / band : r % tiles_n) * BN;
     float *out = p.out + bz * p.o_bstride;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    block_barrier();                      // previous tile's last LDS reads are done
+    lds_barrier();                      // previous tile's last LDS reads are done
 #ifdef MFTX_TIMING
     unsigned long long tt0, tt1 = 0, tt2 = 0;       // tile phases: [8] prologue, [9] K loop, [10] epilogue, [11] tiles
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt0));
@@ -781,7 +682,7 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs &p, int vt0) {
             // every wave agrees (barrier)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             wait_vmcnt<0>();
-            block_barrier();
+            lds_barrier();
         }
         if (more) read_frags(buf ^ 1, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -817,7 +718,7 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs &p, int vt0) {
         fetch(0);
         if (T > 1) fetch(1);
         wait_vmcnt<0>();
-        block_barrier();
+        lds_barrier();
         f16x8 fb16[2][TN][3];               // weights of this / the next chunk
         f16x8 fa16[2][3];                   // A row tile i in set (i + parity) & 1
         auto read_b = [&](int buf, int j, int set) {
@@ -847,7 +748,7 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs &p, int vt0) {
                 if (i == BAR) {
                     if (!(MFTX_SABL & 4)) {
                         wait_vmcnt<0>();             // own pieces of chunk c + 1
-                        block_barrier();
+                        lds_barrier();
                     }
                     fetch_begin();
                 }
@@ -895,16 +796,16 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs &p, int vt0) {
             for (int i = 0; i < NS; ++i)
                 if (i < T) fetch(i);
             if (T >= NS) wait_vmcnt<(NS - 1) * L>(); else wait_vmcnt<0>();
-            block_barrier();
+            lds_barrier();
             int slot = 0;
             for (int c = 0; c + 1 < T; ++c) {
                 if (c + NS - 1 < T) wait_vmcnt<(NS - 2) * L>(); else wait_vmcnt<0>();
-                block_barrier();
+                lds_barrier();
                 if (c + NS < T) fetch(slot);
                 slot = slot + 1 == NS ? 0 : slot + 1;
             }
         } else {
-            block_barrier();
+            lds_barrier();
             read_raw(0, 0, 0);
             ah[0] = __builtin_bit_cast(f16x8, ra[0][0][0]);
             al[0] = __builtin_bit_cast(f16x8, ra[0][0][1]);
@@ -916,7 +817,7 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs &p, int vt0) {
                 group(0, 1, std::true_type{}, std::false_type{}, 0);
                 if constexpr (more) {
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    block_barrier();
+                    lds_barrier();
                     read_raw(nslot, 0, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -940,7 +841,7 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs &p, int vt0) {
         for (int i = 0; i < NS; ++i)
             if (i < T) fetch(i);
         if (T >= NS) wait_vmcnt<(NS - 1) * L>(); else wait_vmcnt<0>();
-        block_barrier();
+        lds_barrier();
         read_raw(0, 0, 0);
         if ((MFTX_SABL & 1) || PRE) {
             ah[0] = __builtin_bit_cast(f16x8, ra[0][0][0]);
@@ -980,7 +881,7 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs &p, int vt0) {
                     if constexpr (decltype(refill_)::value || NS == 2) wait_vmcnt<(NS - 2) * L>();      // (steady part: chunks c + 1 .. c + NS - 1 are in flight)
                     else if (c + NS - 1 < T) wait_vmcnt<(NS - 2) * L>(); else wait_vmcnt<0>();
                     STAMP(3);
-                    block_barrier();
+                    lds_barrier();
                     STAMP(4);
                 }
                 read_raw(nslot, 0, 0);
@@ -1017,7 +918,7 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs &p, int vt0) {
     } else {
         wait_vmcnt<0>();
     }
-    block_barrier();
+    lds_barrier();
     read_frags(0, 0, 0);
     int it = 0;
     for (; it + 3 < T; it += 2) {
@@ -1054,7 +955,7 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs &p, int vt0) {
     if constexpr (EPI == EPI_VOLUME) {
         static_assert(MT == 32 && TM == 1 && TN == 4 && WN == 1 && BN == 128, "volume tile: 32 queries x one super-block per wave");
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        block_barrier();                      // every wave is done with the ring: it becomes epilogue staging
+        lds_barrier();                      // every wave is done with the ring: it becomes epilogue staging
         if (!(MFTX_SABL & 32)) volume_epilogue(p, acc[0], smem + wid * 4096, lane, m0 + wm * 32, n0 / BN, bz);
 #ifdef MFTX_TIMING
         {
@@ -1074,7 +975,7 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs &p, int vt0) {
         // C/D layout's 4-byte ones (the epilogue is issue-bound: 64 stores per 64 x 64 wave tile), same 128-byte runs
         // per row.  Two phases per tile as below: every global read first, then arithmetic and stores.
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        block_barrier();                      // every wave is done with the ring: it becomes epilogue staging
+        lds_barrier();                      // every wave is done with the ring: it becomes epilogue staging
         if (WS && is_prod) continue;          // (producer waves hold no accumulators: on to the next tile's top barrier)
         // (16-row MFMA tiles: the epilogue tile is one 16-row tile x the wave's 64 columns -- four passes of 4 rows x 16
         // float4; staging rows padded to 68 floats so that the four lane groups' C/D writes spread over all banks)

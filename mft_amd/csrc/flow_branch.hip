@@ -24,13 +24,9 @@
 // gives NaN, never a finite wrong value.
 #include "common.h"
 #include "profile.h"
+#include "device_prims.h"
 
 namespace mftx {
-
-typedef float fb_f32x16 __attribute__((ext_vector_type(16)));
-typedef float fb_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned fb_u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 fb_f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int FB_TH = 8, FB_TW = 16;                 // output tile (cells)
 constexpr int FB_HW = FB_TW + 2;                     // halo tile: 10 x 18 cells
@@ -72,64 +68,6 @@ struct FlowBranchArgs {
     int P, h, w, tiles_x, tiles_y;
 };
 
-__device__ __forceinline__ void fb_barrier() {
-    // s_waitcnt lgkmcnt(0): gfx950 has back-off barriers, so the compiler inserts NO wait in front of s_barrier and the builtin is no
-    // fence -- without this a wave's last ds_write may still sit in the LDS queue when another wave reads the slot behind the
-    // barrier (found in round 5 with tools/race_kernels.py: harmless with the GPU to itself, wrong values under contention).
-    // LDS only: global prefetches and LDS-DMA loads (vmcnt) stay in flight, their consumers count them themselves.
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-// hi / lo halves of 8 consecutive k (conv_gemm.hip: split8)
-__device__ __forceinline__ void fb_split8(const fb_f32x4 &u, const fb_f32x4 &v, float k2048, fb_f16x8 &hi, fb_f16x8 &lo) {
-    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-    float r0, r1, r2, r3, r4, r5, r6, r7;
-    asm("v_cvt_pk_f16_f32 %0, %16, %17\n\t"
-        "v_cvt_pk_f16_f32 %1, %18, %19\n\t"
-        "v_cvt_pk_f16_f32 %2, %20, %21\n\t"
-        "v_cvt_pk_f16_f32 %3, %22, %23\n\t"
-        "v_fma_mix_f32 %8, %0, -1.0, %16 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %9, %0, -1.0, %17 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %10, %1, -1.0, %18 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %11, %1, -1.0, %19 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %12, %2, -1.0, %20 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %13, %2, -1.0, %21 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %14, %3, -1.0, %22 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %15, %3, -1.0, %23 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixlo_f16 %4, %8, %24, 0\n\t"
-        "v_fma_mixlo_f16 %5, %10, %24, 0\n\t"
-        "v_fma_mixlo_f16 %6, %12, %24, 0\n\t"
-        "v_fma_mixlo_f16 %7, %14, %24, 0\n\t"
-        "v_fma_mixhi_f16 %4, %9, %24, 0\n\t"
-        "v_fma_mixhi_f16 %5, %11, %24, 0\n\t"
-        "v_fma_mixhi_f16 %6, %13, %24, 0\n\t"
-        "v_fma_mixhi_f16 %7, %15, %24, 0\n\t"
-        "s_nop 1"
-        : "=&v"(h0), "=&v"(h1), "=&v"(h2), "=&v"(h3), "=&v"(l0), "=&v"(l1), "=&v"(l2), "=&v"(l3),
-          "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5), "=&v"(r6), "=&v"(r7)
-        : "v"(u[0]), "v"(u[1]), "v"(u[2]), "v"(u[3]), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "s"(k2048));
-    hi = __builtin_bit_cast(fb_f16x8, fb_u32x4{h0, h1, h2, h3});
-    lo = __builtin_bit_cast(fb_f16x8, fb_u32x4{l0, l1, l2, l3});
-}
-
-// the same for two values (conv_gemm.hip: split_pair)
-__device__ __forceinline__ void fb_split_pair(float x0, float x1, float k2048, unsigned &h, unsigned &l) {
-    float r0, r1;
-    asm("v_cvt_pk_f16_f32 %0, %4, %5\n\t"
-        "v_fma_mix_f32 %2, %0, -1.0, %4 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %3, %0, -1.0, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixlo_f16 %1, %2, %6, 0\n\t"
-        "v_fma_mixhi_f16 %1, %3, %6, 0"
-        : "=&v"(h), "=&v"(l), "=&v"(r0), "=&v"(r1)
-        : "v"(x0), "v"(x1), "s"(k2048));
-}
-
-__device__ __forceinline__ fb_f32x16 fb_mfma(const fb_f16x8 &a, const fb_f16x8 &b, const fb_f32x16 &c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
 __global__ __launch_bounds__(512, 2) void flow_branch_kernel(FlowBranchArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char fb_lds[];
     unsigned char *lds = fb_lds;
@@ -147,18 +85,18 @@ __global__ __launch_bounds__(512, 2) void flow_branch_kernel(FlowBranchArgs p) {
 
     // ---- stage 1 weights: this wave's 32 channels (column tile j1), all 7 filter rows -> registers
     const int j1 = wv & 3;
-    fb_f16x8 w1h[7], w1l[7];
+    f16x8 w1h[7], w1l[7];
 #pragma unroll
     for (int g = 0; g < 7; ++g) {
         const uint4 *src = wf + ((g * 4 + j1) * 2) * 64 + lane;
-        w1h[g] = __builtin_bit_cast(fb_f16x8, src[0]);
-        w1l[g] = __builtin_bit_cast(fb_f16x8, src[64]);
+        w1h[g] = __builtin_bit_cast(f16x8, src[0]);
+        w1l[g] = __builtin_bit_cast(f16x8, src[64]);
     }
     // (stage 1 computes the TRANSPOSED product, channels x cells: a lane ends up with 4 x 4 consecutive channels of ONE cell --
     // channels 32 j1 + 8 b + 4 (lane >> 5) + 0..3 for b = 0..3)
-    fb_f32x4 bias1[4];
+    f32x4 bias1[4];
 #pragma unroll
-    for (int b = 0; b < 4; ++b) bias1[b] = *reinterpret_cast<const fb_f32x4 *>(p.b1 + 32 * j1 + 8 * b + 4 * (lane >> 5));
+    for (int b = 0; b < 4; ++b) bias1[b] = *reinterpret_cast<const f32x4 *>(p.b1 + 32 * j1 + 8 * b + 4 * (lane >> 5));
 
     // ---- stage 0: flow tile -> LDS
     // The flow is split ONCE, here: cell (r, c) -> (hi_x | hi_y << 16) and (lo_x | lo_y << 16).  An A fragment of stage 1 is
@@ -218,7 +156,7 @@ __global__ __launch_bounds__(512, 2) void flow_branch_kernel(FlowBranchArgs p) {
         }
     }
     FB_T(2);
-    fb_barrier();
+    lds_barrier();
     FB_T(3);
 
     // ---- stage 1: convf1 on the halo cells: 6 row tiles x 4 column tiles = 24 tiles of 32 x 32, three per wave (column tile
@@ -236,23 +174,23 @@ __global__ __launch_bounds__(512, 2) void flow_branch_kernel(FlowBranchArgs p) {
             const unsigned char *arow = lds + FB_OFF_FLOW + (((sft * 2) * 16 + ry) * FB_FROW + (c0 - sft)) * 4;
             // (slots 14, 15 of a filter row carry zero weights: zero operands too, or a non-finite flow one column further would reach this cell as NaN x 0)
             const unsigned padmask = (lane >> 5) ? 0u : 0xffffffffu;
-            fb_f32x16 acc1, accx1;
+            f32x16 acc1, accx1;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { acc1[r] = 0.f; accx1[r] = 0.f; }
-            fb_u32x4 ahw[7], alw[7];
+            u32x4 ahw[7], alw[7];
 #pragma unroll
             for (int g = 0; g < 7; ++g) {
-                ahw[g] = *reinterpret_cast<const fb_u32x4 *>(arow + g * FB_FROW * 4);
-                alw[g] = *reinterpret_cast<const fb_u32x4 *>(arow + (16 + g) * FB_FROW * 4);
+                ahw[g] = *reinterpret_cast<const u32x4 *>(arow + g * FB_FROW * 4);
+                alw[g] = *reinterpret_cast<const u32x4 *>(arow + (16 + g) * FB_FROW * 4);
             }
 #pragma unroll
             for (int g = 0; g < 7; ++g) {
                 ahw[g][3] &= padmask;
                 alw[g][3] &= padmask;
-                const fb_f16x8 ah = __builtin_bit_cast(fb_f16x8, ahw[g]), al = __builtin_bit_cast(fb_f16x8, alw[g]);
-                acc1 = fb_mfma(w1h[g], ah, acc1);
-                accx1 = fb_mfma(w1l[g], ah, accx1);
-                accx1 = fb_mfma(w1h[g], al, accx1);
+                const f16x8 ah = __builtin_bit_cast(f16x8, ahw[g]), al = __builtin_bit_cast(f16x8, alw[g]);
+                acc1 = mfma_f16(w1h[g], ah, acc1);
+                accx1 = mfma_f16(w1l[g], ah, accx1);
+                accx1 = mfma_f16(w1h[g], al, accx1);
             }
             FB_T(4);
             const int yy = y0 - 1 + ry, xx = x0 - 1 + rx;
@@ -267,21 +205,21 @@ __global__ __launch_bounds__(512, 2) void flow_branch_kernel(FlowBranchArgs p) {
                     v[e] = (t + __builtin_fabsf(t)) * 0.5f;       // relu that keeps NaN (2 t is exact)
                 }
                 unsigned h0, l0, h1, l1;
-                fb_split_pair(v[0], v[1], k2048, h0, l0);
-                fb_split_pair(v[2], v[3], k2048, h1, l1);
+                split_pair(v[0], v[1], k2048, h0, l0);
+                split_pair(v[2], v[3], k2048, h1, l1);
                 *reinterpret_cast<uint2 *>(cellp + b * 32) = make_uint2(h0 & keep, h1 & keep);
                 *reinterpret_cast<uint2 *>(cellp + b * 32 + 16) = make_uint2(l0 & keep, l1 & keep);
             }
             FB_T(5);
         }
     }
-    fb_barrier();
+    lds_barrier();
     FB_T(6);
 
     // ---- stage 2: convf2.  Wave (nt, kq): output channels [32 nt, 32 nt + 32) of all four row tiles, channel groups 2 kq, 2 kq + 1 of every tap
     const int nt = wv & 1, kq = wv >> 1;
     const uint4 *__restrict__ w2 = wf + FB_W1_BYTES / 16 + (nt * 4 + kq) * 18 * 128 + lane;
-    fb_f32x16 acc[4], accx[4];
+    f32x16 acc[4], accx[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -300,36 +238,36 @@ __global__ __launch_bounds__(512, 2) void flow_branch_kernel(FlowBranchArgs p) {
     uint4 bq[PF][2];
 #pragma unroll
     for (int s = 0; s < PF; ++s) { bq[s][0] = w2[s * 128]; bq[s][1] = w2[s * 128 + 64]; }
-    fb_f16x8 ah[2][4], al[2][4];
+    f16x8 ah[2][4], al[2][4];
     auto read_a = [&](int s, int set) {
         const int tap = s >> 1, gg = s & 1;
         const int off = ((tap / 3) * FB_HW + tap % 3) * FB_CELL + gg * 64;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            ah[set][i] = *reinterpret_cast<const fb_f16x8 *>(abase[i] + off);
-            al[set][i] = *reinterpret_cast<const fb_f16x8 *>(abase[i] + off + 16);
+            ah[set][i] = *reinterpret_cast<const f16x8 *>(abase[i] + off);
+            al[set][i] = *reinterpret_cast<const f16x8 *>(abase[i] + off + 16);
         }
     };
     read_a(0, 0);
 #pragma unroll
     for (int s = 0; s < 18; ++s) {
         const int set = s & 1;
-        const fb_f16x8 bh = __builtin_bit_cast(fb_f16x8, bq[s % PF][0]), bl = __builtin_bit_cast(fb_f16x8, bq[s % PF][1]);
+        const f16x8 bh = __builtin_bit_cast(f16x8, bq[s % PF][0]), bl = __builtin_bit_cast(f16x8, bq[s % PF][1]);
         __builtin_amdgcn_sched_barrier(0);
         if (s + 1 < 18) read_a(s + 1, set ^ 1);
         if (s + PF < 18) { bq[s % PF][0] = w2[(s + PF) * 128]; bq[s % PF][1] = w2[(s + PF) * 128 + 64]; }
         __builtin_amdgcn_sched_barrier(0);
         // (weights first: D = W2 x features^T, channels x cells -- a lane ends up with 4 x 4 consecutive channels of one cell per row tile)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = fb_mfma(bh, ah[set][i], acc[i]);
+        for (int i = 0; i < 4; ++i) acc[i] = mfma_f16(bh, ah[set][i], acc[i]);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) accx[i] = fb_mfma(bl, ah[set][i], accx[i]);
+        for (int i = 0; i < 4; ++i) accx[i] = mfma_f16(bl, ah[set][i], accx[i]);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) accx[i] = fb_mfma(bh, al[set][i], accx[i]);
+        for (int i = 0; i < 4; ++i) accx[i] = mfma_f16(bh, al[set][i], accx[i]);
         __builtin_amdgcn_sched_barrier(0);
     }
     FB_T(7);
-    fb_barrier();           // every wave is done with the feature tile: its space takes the partial sums
+    lds_barrier();           // every wave is done with the feature tile: its space takes the partial sums
 
     // ---- stage 3: the four K quarters -> LDS [kq][cell][channel], summed in the order kq = 0, 1, 2, 3
     float *red = reinterpret_cast<float *>(lds);
@@ -337,30 +275,30 @@ __global__ __launch_bounds__(512, 2) void flow_branch_kernel(FlowBranchArgs p) {
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-            fb_f32x4 v;
+            f32x4 v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = acc[i][4 * b + e] + accx[i][4 * b + e] * inv2048;
-            *reinterpret_cast<fb_f32x4 *>(red + (kq * 128 + 32 * i + (lane & 31)) * FB_RED_ROW + 32 * nt + 8 * b + 4 * (lane >> 5)) = v;
+            *reinterpret_cast<f32x4 *>(red + (kq * 128 + 32 * i + (lane & 31)) * FB_RED_ROW + 32 * nt + 8 * b + 4 * (lane >> 5)) = v;
         }
     FB_T(8);
-    fb_barrier();
+    lds_barrier();
     FB_T(9);
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
         const int item = tid + 512 * it, m = item >> 3, g8 = item & 7;
         const int yy = y0 + (m >> 4), xx = x0 + (m & 15);
         const float *src = red + m * FB_RED_ROW + 8 * g8;
-        fb_f32x4 u = *reinterpret_cast<const fb_f32x4 *>(src), v = *reinterpret_cast<const fb_f32x4 *>(src + 4);
+        f32x4 u = *reinterpret_cast<const f32x4 *>(src), v = *reinterpret_cast<const f32x4 *>(src + 4);
 #pragma unroll
         for (int q = 1; q < 4; ++q) {
-            u += *reinterpret_cast<const fb_f32x4 *>(src + q * 128 * FB_RED_ROW);
-            v += *reinterpret_cast<const fb_f32x4 *>(src + q * 128 * FB_RED_ROW + 4);
+            u += *reinterpret_cast<const f32x4 *>(src + q * 128 * FB_RED_ROW);
+            v += *reinterpret_cast<const f32x4 *>(src + q * 128 * FB_RED_ROW + 4);
         }
-        const fb_f32x4 bu = *reinterpret_cast<const fb_f32x4 *>(p.b2 + 8 * g8), bv = *reinterpret_cast<const fb_f32x4 *>(p.b2 + 8 * g8 + 4);
+        const f32x4 bu = *reinterpret_cast<const f32x4 *>(p.b2 + 8 * g8), bv = *reinterpret_cast<const f32x4 *>(p.b2 + 8 * g8 + 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) { u[e] = relu_keep_nan(u[e] + bu[e]); v[e] = relu_keep_nan(v[e] + bv[e]); }
-        fb_f16x8 hi, lo;
-        fb_split8(u, v, k2048, hi, lo);
+        f16x8 hi, lo;
+        split8(u, v, k2048, hi, lo);
         if (yy < p.h && xx < p.w) {
             const long long cell = img_base + (long long)yy * p.w + xx;
             uint4 *dst = reinterpret_cast<uint4 *>(reinterpret_cast<char *>(p.out + cell * p.ld_out) + g8 * 32);

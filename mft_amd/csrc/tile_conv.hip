@@ -24,13 +24,9 @@
 // go to their accumulator in another order for N = 128): fp32 rounding.
 #include "common.h"
 #include "profile.h"
+#include "device_prims.h"
 
 namespace mftx {
-
-typedef float tc_f32x16 __attribute__((ext_vector_type(16)));
-typedef float tc_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned tc_u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 tc_f16x8 __attribute__((ext_vector_type(8)));
 
 enum TcEpi { TC_LINEAR = 0, TC_RELU = 1, TC_GRU_ZR = 2, TC_GRU_Q = 3,
              TC_RELU_PROJ = 4 };     // relu(. + bias) is not stored: it is multiplied, in place, with the NEXT layer's 3 x 3 x 2 filter (see below)
@@ -62,78 +58,6 @@ struct TileConvArgs {
     const void *wproj; float *tout;                 // TC_RELU_PROJ: the next layer's filter (launch_pack_flow_head) and the [M][18] partial products
     int P, h, w, tiles_x, tiles_y;
 };
-
-__device__ __forceinline__ void tc_barrier() {
-    // s_waitcnt lgkmcnt(0): gfx950 has back-off barriers, so the compiler inserts NO wait in front of s_barrier and the builtin is no
-    // fence -- without this a wave's last ds_write may still sit in the LDS queue when another wave reads the slot behind the
-    // barrier (found in round 5 with tools/race_kernels.py: harmless with the GPU to itself, wrong values under contention).
-    // LDS only: global prefetches and LDS-DMA loads (vmcnt) stay in flight, their consumers count them themselves.
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ tc_f32x16 tc_mfma(const tc_f16x8 &a, const tc_f16x8 &b, const tc_f32x16 &c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-// hi / lo halves of 8 consecutive values (conv_gemm.hip: split8)
-__device__ __forceinline__ void tc_split8(const tc_f32x4 &u, const tc_f32x4 &v, float k2048, tc_u32x4 &hi, tc_u32x4 &lo) {
-    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-    float r0, r1, r2, r3, r4, r5, r6, r7;
-    asm("v_cvt_pk_f16_f32 %0, %16, %17\n\t"
-        "v_cvt_pk_f16_f32 %1, %18, %19\n\t"
-        "v_cvt_pk_f16_f32 %2, %20, %21\n\t"
-        "v_cvt_pk_f16_f32 %3, %22, %23\n\t"
-        "v_fma_mix_f32 %8, %0, -1.0, %16 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %9, %0, -1.0, %17 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %10, %1, -1.0, %18 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %11, %1, -1.0, %19 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %12, %2, -1.0, %20 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %13, %2, -1.0, %21 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %14, %3, -1.0, %22 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %15, %3, -1.0, %23 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixlo_f16 %4, %8, %24, 0\n\t"
-        "v_fma_mixlo_f16 %5, %10, %24, 0\n\t"
-        "v_fma_mixlo_f16 %6, %12, %24, 0\n\t"
-        "v_fma_mixlo_f16 %7, %14, %24, 0\n\t"
-        "v_fma_mixhi_f16 %4, %9, %24, 0\n\t"
-        "v_fma_mixhi_f16 %5, %11, %24, 0\n\t"
-        "v_fma_mixhi_f16 %6, %13, %24, 0\n\t"
-        "v_fma_mixhi_f16 %7, %15, %24, 0"
-        : "=&v"(h0), "=&v"(h1), "=&v"(h2), "=&v"(h3), "=&v"(l0), "=&v"(l1), "=&v"(l2), "=&v"(l3),
-          "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5), "=&v"(r6), "=&v"(r7)
-        : "v"(u[0]), "v"(u[1]), "v"(u[2]), "v"(u[3]), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "s"(k2048));
-    hi = tc_u32x4{h0, h1, h2, h3};
-    lo = tc_u32x4{l0, l1, l2, l3};
-}
-
-// ... and of 4 consecutive values (the same operations per value: the same bits)
-__device__ __forceinline__ void tc_split4(const tc_f32x4 &u, float k2048, unsigned (&hi)[2], unsigned (&lo)[2]) {
-    unsigned h0, h1, l0, l1;
-    float r0, r1, r2, r3;
-    asm("v_cvt_pk_f16_f32 %0, %8, %9\n\t"
-        "v_cvt_pk_f16_f32 %1, %10, %11\n\t"
-        "v_fma_mix_f32 %4, %0, -1.0, %8 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %5, %0, -1.0, %9 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %6, %1, -1.0, %10 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %7, %1, -1.0, %11 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixlo_f16 %2, %4, %12, 0\n\t"
-        "v_fma_mixlo_f16 %3, %6, %12, 0\n\t"
-        "v_fma_mixhi_f16 %2, %5, %12, 0\n\t"
-        "v_fma_mixhi_f16 %3, %7, %12, 0"
-        : "=&v"(h0), "=&v"(h1), "=&v"(l0), "=&v"(l1), "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)
-        : "v"(u[0]), "v"(u[1]), "v"(u[2]), "v"(u[3]), "s"(k2048));
-    hi[0] = h0; hi[1] = h1; lo[0] = l0; lo[1] = l1;
-}
-
-// the gate algebra, as conv_gemm.hip spells it (same functions: the two kernels agree to fp32 rounding of the K sum)
-__device__ __forceinline__ float tc_sigmoid(float s) { return __frcp_rn(1.f + __expf(-s)); }
-__device__ __forceinline__ float tc_tanh(float s) {
-    const float t = __expf(-2.f * fabsf(s));
-    return copysignf((1.f - t) * __frcp_rn(1.f + t), s);
-}
-__device__ __forceinline__ float tc_blend(float z, float h, float q) { return __fmaf_rn(z, q, __fmul_rn(__fsub_rn(1.f, z), h)); }
 
 template <int TH, int TW, int KH, int KW, int CIN, int N>
 struct TcGeom {
@@ -208,11 +132,11 @@ __global__ __launch_bounds__(512, 2) void tile_conv_kernel(TileConvArgs p) {
         }
     }
     TC_T(2);
-    tc_barrier();
+    lds_barrier();
     TC_T(3);
 
     // ---- the K loop
-    tc_f32x16 acc[G::RT], accx[G::RT];
+    f32x16 acc[G::RT], accx[G::RT];
 #pragma unroll
     for (int i = 0; i < G::RT; ++i)
 #pragma unroll
@@ -226,35 +150,35 @@ __global__ __launch_bounds__(512, 2) void tile_conv_kernel(TileConvArgs p) {
             abase[i] = lds + ((m / TW) * G::HWD + (m % TW)) * G::CELLB + (lane >> 5) * 32 + ks * 64;
         }
     }
-    tc_f16x8 ah[2][G::RT], al[2][G::RT];
+    f16x8 ah[2][G::RT], al[2][G::RT];
     auto read_a = [&](int s, int set) {
         const int tap = s / G::GPW, gg = s % G::GPW;
         const int off = ((tap / KW) * G::HWD + tap % KW) * G::CELLB + gg * 64 * G::KS;
 #pragma unroll
         for (int i = 0; i < G::RT; ++i) {
-            ah[set][i] = *reinterpret_cast<const tc_f16x8 *>(abase[i] + off);
-            al[set][i] = *reinterpret_cast<const tc_f16x8 *>(abase[i] + off + 16);
+            ah[set][i] = *reinterpret_cast<const f16x8 *>(abase[i] + off);
+            al[set][i] = *reinterpret_cast<const f16x8 *>(abase[i] + off + 16);
         }
     };
     read_a(0, 0);
 #pragma unroll
     for (int s = 0; s < G::STEPS; ++s) {
         const int set = s & 1;
-        const tc_f16x8 bh = __builtin_bit_cast(tc_f16x8, bq[s % PF][0]), bl = __builtin_bit_cast(tc_f16x8, bq[s % PF][1]);
+        const f16x8 bh = __builtin_bit_cast(f16x8, bq[s % PF][0]), bl = __builtin_bit_cast(f16x8, bq[s % PF][1]);
         __builtin_amdgcn_sched_barrier(0);
         if (s + 1 < G::STEPS) read_a(s + 1, set ^ 1);
         if (s + PF < G::STEPS) { bq[s % PF][0] = w2[(s + PF) * 128]; bq[s % PF][1] = w2[(s + PF) * 128 + 64]; }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int i = 0; i < G::RT; ++i) acc[i] = tc_mfma(bh, ah[set][i], acc[i]);
+        for (int i = 0; i < G::RT; ++i) acc[i] = mfma_f16(bh, ah[set][i], acc[i]);
 #pragma unroll
-        for (int i = 0; i < G::RT; ++i) accx[i] = tc_mfma(bl, ah[set][i], accx[i]);
+        for (int i = 0; i < G::RT; ++i) accx[i] = mfma_f16(bl, ah[set][i], accx[i]);
 #pragma unroll
-        for (int i = 0; i < G::RT; ++i) accx[i] = tc_mfma(bh, al[set][i], accx[i]);
+        for (int i = 0; i < G::RT; ++i) accx[i] = mfma_f16(bh, al[set][i], accx[i]);
         __builtin_amdgcn_sched_barrier(0);
     }
     TC_T(4);
-    tc_barrier();           // every wave is done with the input tile: its space takes the sums
+    lds_barrier();           // every wave is done with the input tile: its space takes the sums
     TC_T(5);
 
     // ---- sums -> LDS [K split][cell][channel]
@@ -264,13 +188,13 @@ __global__ __launch_bounds__(512, 2) void tile_conv_kernel(TileConvArgs p) {
     for (int i = 0; i < G::RT; ++i)
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-            tc_f32x4 v;
+            f32x4 v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = acc[i][4 * b + e] + accx[i][4 * b + e] * inv2048;
-            *reinterpret_cast<tc_f32x4 *>(red + (ks * G::CELLS + 32 * i + (lane & 31)) * G::RED_ROW + 32 * nt + 8 * b + 4 * (lane >> 5)) = v;
+            *reinterpret_cast<f32x4 *>(red + (ks * G::CELLS + 32 * i + (lane & 31)) * G::RED_ROW + 32 * nt + 8 * b + 4 * (lane >> 5)) = v;
         }
     TC_T(6);
-    tc_barrier();
+    lds_barrier();
     TC_T(7);
 
     const float k2048 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(0x45000000));
@@ -286,39 +210,39 @@ __global__ __launch_bounds__(512, 2) void tile_conv_kernel(TileConvArgs p) {
         const uint4 *__restrict__ wp = reinterpret_cast<const uint4 *>(p.wproj) + lane;
         float *tp = reinterpret_cast<float *>(lds + G::RED_BYTES);
         if (mt < G::RT) {
-        tc_f32x16 d, dx;
+        f32x16 d, dx;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { d[r] = 0.f; dx[r] = 0.f; }
         const float *xrow = red + (32 * mt + (lane & 31)) * G::RED_ROW + 8 * (lane >> 5);
 #pragma unroll
         for (int gg = 0; gg < 8; ++gg) {
             const int g = 8 * kh + gg;
-            tc_f32x4 u = *reinterpret_cast<const tc_f32x4 *>(xrow + 16 * g), v = *reinterpret_cast<const tc_f32x4 *>(xrow + 16 * g + 4);
-            u += *reinterpret_cast<const tc_f32x4 *>(p.bias + 16 * g + 8 * (lane >> 5));
-            v += *reinterpret_cast<const tc_f32x4 *>(p.bias + 16 * g + 8 * (lane >> 5) + 4);
+            f32x4 u = *reinterpret_cast<const f32x4 *>(xrow + 16 * g), v = *reinterpret_cast<const f32x4 *>(xrow + 16 * g + 4);
+            u += *reinterpret_cast<const f32x4 *>(p.bias + 16 * g + 8 * (lane >> 5));
+            v += *reinterpret_cast<const f32x4 *>(p.bias + 16 * g + 8 * (lane >> 5) + 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { u[e] = relu_keep_nan(u[e]); v[e] = relu_keep_nan(v[e]); }
-            tc_u32x4 hi, lo;
-            tc_split8(u, v, k2048, hi, lo);
-            const tc_f16x8 wh = __builtin_bit_cast(tc_f16x8, wp[(g * 2) * 64]), wl = __builtin_bit_cast(tc_f16x8, wp[(g * 2 + 1) * 64]);
+            u32x4 hi, lo;
+            split8_raw(u, v, k2048, hi, lo);
+            const f16x8 wh = __builtin_bit_cast(f16x8, wp[(g * 2) * 64]), wl = __builtin_bit_cast(f16x8, wp[(g * 2 + 1) * 64]);
             asm volatile("s_nop 1" : "+v"(hi), "+v"(lo));      // (the split's results, two wait states before the MFMA reads them)
-            const tc_f16x8 xh = __builtin_bit_cast(tc_f16x8, hi), xl = __builtin_bit_cast(tc_f16x8, lo);
-            d = tc_mfma(wh, xh, d);
-            dx = tc_mfma(wl, xh, dx);
-            dx = tc_mfma(wh, xl, dx);
+            const f16x8 xh = __builtin_bit_cast(f16x8, hi), xl = __builtin_bit_cast(f16x8, lo);
+            d = mfma_f16(wh, xh, d);
+            dx = mfma_f16(wl, xh, dx);
+            dx = mfma_f16(wh, xl, dx);
         }
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const int j0 = 8 * b + 4 * (lane >> 5);          // this lane's outputs j0 .. j0 + 3 of cell 32 mt + (lane & 31); 18 exist
             if (j0 < G::PROJ_ROW) {
-                tc_f32x4 v;
+                f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = d[4 * b + e] + dx[4 * b + e] * inv2048;
-                *reinterpret_cast<tc_f32x4 *>(tp + (kh * G::CELLS + 32 * mt + (lane & 31)) * G::PROJ_ROW + j0) = v;
+                *reinterpret_cast<f32x4 *>(tp + (kh * G::CELLS + 32 * mt + (lane & 31)) * G::PROJ_ROW + j0) = v;
             }
         }
         }
-        tc_barrier();
+        lds_barrier();
         for (int idx = tid; idx < G::CELLS * 18; idx += 512) {
             const int m = idx / 18, j = idx - m * 18;
             const int yy = y0 + m / TW, xx = x0 + m % TW;
@@ -337,47 +261,47 @@ __global__ __launch_bounds__(512, 2) void tile_conv_kernel(TileConvArgs p) {
         const int item = tid + 512 * it, m = item / GPC, n0 = (item % GPC) * 8;
         const int yy = y0 + m / TW, xx = x0 + m % TW;
         const float *src = red + m * G::RED_ROW + n0;
-        tc_f32x4 u = *reinterpret_cast<const tc_f32x4 *>(src), v = *reinterpret_cast<const tc_f32x4 *>(src + 4);
+        f32x4 u = *reinterpret_cast<const f32x4 *>(src), v = *reinterpret_cast<const f32x4 *>(src + 4);
         if constexpr (G::KS == 2) {
-            u += *reinterpret_cast<const tc_f32x4 *>(src + G::CELLS * G::RED_ROW);
-            v += *reinterpret_cast<const tc_f32x4 *>(src + G::CELLS * G::RED_ROW + 4);
+            u += *reinterpret_cast<const f32x4 *>(src + G::CELLS * G::RED_ROW);
+            v += *reinterpret_cast<const f32x4 *>(src + G::CELLS * G::RED_ROW + 4);
         }
         if (yy >= p.h || xx >= p.w) continue;
         const long long cell = img_base + (long long)yy * p.w + xx;
         if (p.bias) {
-            u += *reinterpret_cast<const tc_f32x4 *>(p.bias + n0);
-            v += *reinterpret_cast<const tc_f32x4 *>(p.bias + n0 + 4);
+            u += *reinterpret_cast<const f32x4 *>(p.bias + n0);
+            v += *reinterpret_cast<const f32x4 *>(p.bias + n0 + 4);
         }
         if (p.addend) {
-            u += *reinterpret_cast<const tc_f32x4 *>(p.addend + cell * p.ld_addend + n0);
-            v += *reinterpret_cast<const tc_f32x4 *>(p.addend + cell * p.ld_addend + n0 + 4);
+            u += *reinterpret_cast<const f32x4 *>(p.addend + cell * p.ld_addend + n0);
+            v += *reinterpret_cast<const f32x4 *>(p.addend + cell * p.ld_addend + n0 + 4);
         }
         auto store_split = [&](float *row, int c0) {        // 8 channels c0 .. c0 + 7 (c0 % 8 == 0) of a split-form row
-            tc_u32x4 hi, lo;
-            tc_split8(u, v, k2048, hi, lo);
+            u32x4 hi, lo;
+            split8_raw(u, v, k2048, hi, lo);
             uint4 *dst = reinterpret_cast<uint4 *>(reinterpret_cast<char *>(row) + (c0 >> 3) * 32);
             dst[0] = __builtin_bit_cast(uint4, hi);
             dst[1] = __builtin_bit_cast(uint4, lo);
         };
         if constexpr (EPI == TC_GRU_ZR) {                   // [z | r] gates; r is folded into r * h (core/update.py:113-115, 119-121)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { u[e] = tc_sigmoid(u[e]); v[e] = tc_sigmoid(v[e]); }
+            for (int e = 0; e < 4; ++e) { u[e] = fast_sigmoid(u[e]); v[e] = fast_sigmoid(v[e]); }
             if (n0 < 128) {
-                *reinterpret_cast<tc_f32x4 *>(p.z + cell * 128 + n0) = u;
-                *reinterpret_cast<tc_f32x4 *>(p.z + cell * 128 + n0 + 4) = v;
+                *reinterpret_cast<f32x4 *>(p.z + cell * 128 + n0) = u;
+                *reinterpret_cast<f32x4 *>(p.z + cell * 128 + n0 + 4) = v;
             } else {
-                u *= *reinterpret_cast<const tc_f32x4 *>(p.hf + cell * p.ld_hf + n0 - 128);
-                v *= *reinterpret_cast<const tc_f32x4 *>(p.hf + cell * p.ld_hf + n0 - 128 + 4);
+                u *= *reinterpret_cast<const f32x4 *>(p.hf + cell * p.ld_hf + n0 - 128);
+                v *= *reinterpret_cast<const f32x4 *>(p.hf + cell * p.ld_hf + n0 - 128 + 4);
                 store_split(p.rh + cell * 128, n0 - 128);
             }
         } else if constexpr (EPI == TC_GRU_Q) {             // candidate q, h <- (1 - z) h + z q (core/update.py:116-117, 122-123)
-            const tc_f32x4 z0 = *reinterpret_cast<const tc_f32x4 *>(p.z + cell * 128 + n0), z1 = *reinterpret_cast<const tc_f32x4 *>(p.z + cell * 128 + n0 + 4);
+            const f32x4 z0 = *reinterpret_cast<const f32x4 *>(p.z + cell * 128 + n0), z1 = *reinterpret_cast<const f32x4 *>(p.z + cell * 128 + n0 + 4);
             float *hrow = p.hf + cell * p.ld_hf + n0;
-            const tc_f32x4 h0 = *reinterpret_cast<const tc_f32x4 *>(hrow), h1 = *reinterpret_cast<const tc_f32x4 *>(hrow + 4);
+            const f32x4 h0 = *reinterpret_cast<const f32x4 *>(hrow), h1 = *reinterpret_cast<const f32x4 *>(hrow + 4);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { u[e] = tc_blend(z0[e], h0[e], tc_tanh(u[e])); v[e] = tc_blend(z1[e], h1[e], tc_tanh(v[e])); }
-            *reinterpret_cast<tc_f32x4 *>(hrow) = u;
-            *reinterpret_cast<tc_f32x4 *>(hrow + 4) = v;
+            for (int e = 0; e < 4; ++e) { u[e] = gru_blend(z0[e], h0[e], fast_tanh(u[e])); v[e] = gru_blend(z1[e], h1[e], fast_tanh(v[e])); }
+            *reinterpret_cast<f32x4 *>(hrow) = u;
+            *reinterpret_cast<f32x4 *>(hrow + 4) = v;
             store_split(p.hx + cell * p.ld_hx, n0);
         } else {
             if constexpr (EPI == TC_RELU) {
@@ -386,8 +310,8 @@ __global__ __launch_bounds__(512, 2) void tile_conv_kernel(TileConvArgs p) {
             }
             if (p.out_split) store_split(p.out + cell * p.ldo, n0);
             else {
-                *reinterpret_cast<tc_f32x4 *>(p.out + cell * p.ldo + n0) = u;
-                *reinterpret_cast<tc_f32x4 *>(p.out + cell * p.ldo + n0 + 4) = v;
+                *reinterpret_cast<f32x4 *>(p.out + cell * p.ldo + n0) = u;
+                *reinterpret_cast<f32x4 *>(p.out + cell * p.ldo + n0 + 4) = v;
             }
         }
     }
@@ -436,33 +360,33 @@ struct GruHalfArgs {
 
 template <class G, int KW>
 __device__ __forceinline__ void tc_kloop(const unsigned char *const (&abase)[G::RT], const uint4 *__restrict__ w2, uint4 (&bq)[3][2],
-                                         tc_f32x16 (&acc)[G::RT], tc_f32x16 (&accx)[G::RT]) {
+                                         f32x16 (&acc)[G::RT], f32x16 (&accx)[G::RT]) {
     constexpr int PF = 3;
-    tc_f16x8 ah[2][G::RT], al[2][G::RT];
+    f16x8 ah[2][G::RT], al[2][G::RT];
     auto read_a = [&](int s, int set) {
         const int tap = s / G::GPW, gg = s % G::GPW;
         const int off = ((tap / KW) * G::HWD + tap % KW) * G::CELLB + gg * 64 * G::KS;
 #pragma unroll
         for (int i = 0; i < G::RT; ++i) {
-            ah[set][i] = *reinterpret_cast<const tc_f16x8 *>(abase[i] + off);
-            al[set][i] = *reinterpret_cast<const tc_f16x8 *>(abase[i] + off + 16);
+            ah[set][i] = *reinterpret_cast<const f16x8 *>(abase[i] + off);
+            al[set][i] = *reinterpret_cast<const f16x8 *>(abase[i] + off + 16);
         }
     };
     read_a(0, 0);
 #pragma unroll
     for (int s = 0; s < G::STEPS; ++s) {
         const int set = s & 1;
-        const tc_f16x8 bh = __builtin_bit_cast(tc_f16x8, bq[s % PF][0]), bl = __builtin_bit_cast(tc_f16x8, bq[s % PF][1]);
+        const f16x8 bh = __builtin_bit_cast(f16x8, bq[s % PF][0]), bl = __builtin_bit_cast(f16x8, bq[s % PF][1]);
         __builtin_amdgcn_sched_barrier(0);
         if (s + 1 < G::STEPS) read_a(s + 1, set ^ 1);
         if (s + PF < G::STEPS) { bq[s % PF][0] = w2[(s + PF) * 128]; bq[s % PF][1] = w2[(s + PF) * 128 + 64]; }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int i = 0; i < G::RT; ++i) acc[i] = tc_mfma(bh, ah[set][i], acc[i]);
+        for (int i = 0; i < G::RT; ++i) acc[i] = mfma_f16(bh, ah[set][i], acc[i]);
 #pragma unroll
-        for (int i = 0; i < G::RT; ++i) accx[i] = tc_mfma(bl, ah[set][i], accx[i]);
+        for (int i = 0; i < G::RT; ++i) accx[i] = mfma_f16(bl, ah[set][i], accx[i]);
 #pragma unroll
-        for (int i = 0; i < G::RT; ++i) accx[i] = tc_mfma(bh, al[set][i], accx[i]);
+        for (int i = 0; i < G::RT; ++i) accx[i] = mfma_f16(bh, al[set][i], accx[i]);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -537,10 +461,10 @@ __global__ __launch_bounds__(512, 2) void gru_half_kernel(GruHalfArgs p) {
         }
     }
     TC_T(2);
-    tc_barrier();
+    lds_barrier();
     TC_T(3);
 
-    tc_f32x16 acc[RT], accx[RT];
+    f32x16 acc[RT], accx[RT];
     const unsigned char *abase[RT];
     auto zero_acc = [&]() {
 #pragma unroll
@@ -586,28 +510,28 @@ __global__ __launch_bounds__(512, 2) void gru_half_kernel(GruHalfArgs p) {
             const int yc = yy < 0 ? 0 : (yy >= p.h ? p.h - 1 : yy), xc = xx < 0 ? 0 : (xx >= p.w ? p.w - 1 : xx);
             const long long cell = img_base + (long long)yc * p.w + xc;
             const int n0 = 32 * wv + 4 * (lane >> 5);
-            tc_f32x4 a[4], hh[4];
+            f32x4 a[4], hh[4];
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
-                a[b] = *reinterpret_cast<const tc_f32x4 *>(pre_zr + cell * 256 + 128 + n0 + 8 * b);
-                hh[b] = *reinterpret_cast<const tc_f32x4 *>(p.hf_in + cell * 128 + n0 + 8 * b);
+                a[b] = *reinterpret_cast<const f32x4 *>(pre_zr + cell * 256 + 128 + n0 + 8 * b);
+                hh[b] = *reinterpret_cast<const f32x4 *>(p.hf_in + cell * 128 + n0 + 8 * b);
             }
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
-                tc_f32x4 v;
+                f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = acc[i][4 * b + e] + accx[i][4 * b + e] * inv2048;
                 v += a[b];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = tc_sigmoid(v[e]);
+                for (int e = 0; e < 4; ++e) v[e] = fast_sigmoid(v[e]);
                 v *= hh[b];
-                tc_split4(v, k2048, rh_hi[i][b], rh_lo[i][b]);
+                split4(v, k2048, rh_hi[i][b], rh_lo[i][b]);
                 if (!inside) { rh_hi[i][b][0] = rh_hi[i][b][1] = rh_lo[i][b][0] = rh_lo[i][b][1] = 0u; }     // (the candidate's zero padding)
             }
         }
     }
     TC_T(5);
-    tc_barrier();           // every wave is done with the h parts of the tile
+    lds_barrier();           // every wave is done with the h parts of the tile
     // r * h, in place: a cell's 8-channel group is [hi x 8 | lo x 8]; this lane holds channels 4 (lane >> 5) .. + 3 of group 4 wv + b
     if (wv < 4) {
 #pragma unroll
@@ -620,7 +544,7 @@ __global__ __launch_bounds__(512, 2) void gru_half_kernel(GruHalfArgs p) {
             }
         }
     }
-    tc_barrier();
+    lds_barrier();
     TC_T(6);
     // The z waves' sums (acc + accx / 2048, before the context part and the sigmoid) -> global, straight from the accumulators, while
     // their SIMD partners -- older, served first anyway -- are already in the candidate's K loop; stores only: the context part and the
@@ -635,10 +559,10 @@ __global__ __launch_bounds__(512, 2) void gru_half_kernel(GruHalfArgs p) {
             const int n0 = 32 * nt1 + 4 * (lane >> 5);
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
-                tc_f32x4 v;
+                f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = acc[i][4 * b + e] + accx[i][4 * b + e] * inv2048;
-                if (own) *reinterpret_cast<tc_f32x4 *>(p.z + cell * 128 + n0 + 8 * b) = v;
+                if (own) *reinterpret_cast<f32x4 *>(p.z + cell * 128 + n0 + 8 * b) = v;
             }
         }
     }
@@ -649,44 +573,44 @@ __global__ __launch_bounds__(512, 2) void gru_half_kernel(GruHalfArgs p) {
     tc_kloop<G2, KW>(abase, w2, bq, acc, accx);
     TC_T(7);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (this wave's z stores have reached L2 before anyone reads z back)
-    tc_barrier();           // every wave is done with the tile: its space takes the sums
+    lds_barrier();           // every wave is done with the tile: its space takes the sums
     float *red = reinterpret_cast<float *>(lds);
 #pragma unroll
     for (int i = 0; i < RT; ++i)
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-            tc_f32x4 v;
+            f32x4 v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = acc[i][4 * b + e] + accx[i][4 * b + e] * inv2048;
-            *reinterpret_cast<tc_f32x4 *>(red + (ks2 * CELLS + 32 * i + (lane & 31)) * G2::RED_ROW + 32 * nt2 + 8 * b + 4 * (lane >> 5)) = v;
+            *reinterpret_cast<f32x4 *>(red + (ks2 * CELLS + 32 * i + (lane & 31)) * G2::RED_ROW + 32 * nt2 + 8 * b + 4 * (lane >> 5)) = v;
         }
-    tc_barrier();
+    lds_barrier();
     // q = tanh(. + context part), h <- (1 - z) h + z q (core/update.py:116-117, 122-123): the cells this workgroup owns
 #pragma unroll
     for (int it = 0; it < RT; ++it) {
         const int item = tid + 512 * it, m = item >> 4, n0 = (item & 15) * 8;
         const int yy = y0 + m / TW, xx = x0 + m % TW, along = HORIZ ? xx : yy;
         const float *src = red + m * G2::RED_ROW + n0;
-        tc_f32x4 u = *reinterpret_cast<const tc_f32x4 *>(src), v = *reinterpret_cast<const tc_f32x4 *>(src + 4);
-        u += *reinterpret_cast<const tc_f32x4 *>(src + CELLS * G2::RED_ROW);
-        v += *reinterpret_cast<const tc_f32x4 *>(src + CELLS * G2::RED_ROW + 4);
+        f32x4 u = *reinterpret_cast<const f32x4 *>(src), v = *reinterpret_cast<const f32x4 *>(src + 4);
+        u += *reinterpret_cast<const f32x4 *>(src + CELLS * G2::RED_ROW);
+        v += *reinterpret_cast<const f32x4 *>(src + CELLS * G2::RED_ROW + 4);
         if (yy < 0 || yy >= p.h || xx < 0 || xx >= p.w || along < olo || along >= ohi) continue;
         const long long cell = img_base + (long long)yy * p.w + xx;
-        u += *reinterpret_cast<const tc_f32x4 *>(pre_q + cell * 128 + n0);
-        v += *reinterpret_cast<const tc_f32x4 *>(pre_q + cell * 128 + n0 + 4);
-        tc_f32x4 z0 = *reinterpret_cast<const tc_f32x4 *>(p.z + cell * 128 + n0), z1 = *reinterpret_cast<const tc_f32x4 *>(p.z + cell * 128 + n0 + 4);
-        z0 += *reinterpret_cast<const tc_f32x4 *>(pre_zr + cell * 256 + n0);
-        z1 += *reinterpret_cast<const tc_f32x4 *>(pre_zr + cell * 256 + n0 + 4);
+        u += *reinterpret_cast<const f32x4 *>(pre_q + cell * 128 + n0);
+        v += *reinterpret_cast<const f32x4 *>(pre_q + cell * 128 + n0 + 4);
+        f32x4 z0 = *reinterpret_cast<const f32x4 *>(p.z + cell * 128 + n0), z1 = *reinterpret_cast<const f32x4 *>(p.z + cell * 128 + n0 + 4);
+        z0 += *reinterpret_cast<const f32x4 *>(pre_zr + cell * 256 + n0);
+        z1 += *reinterpret_cast<const f32x4 *>(pre_zr + cell * 256 + n0 + 4);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { z0[e] = tc_sigmoid(z0[e]); z1[e] = tc_sigmoid(z1[e]); }
+        for (int e = 0; e < 4; ++e) { z0[e] = fast_sigmoid(z0[e]); z1[e] = fast_sigmoid(z1[e]); }
         const float *hrow = p.hf_in + cell * 128 + n0;
-        const tc_f32x4 h0 = *reinterpret_cast<const tc_f32x4 *>(hrow), h1 = *reinterpret_cast<const tc_f32x4 *>(hrow + 4);
+        const f32x4 h0 = *reinterpret_cast<const f32x4 *>(hrow), h1 = *reinterpret_cast<const f32x4 *>(hrow + 4);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { u[e] = tc_blend(z0[e], h0[e], tc_tanh(u[e])); v[e] = tc_blend(z1[e], h1[e], tc_tanh(v[e])); }
-        *reinterpret_cast<tc_f32x4 *>(p.hf_out + cell * 128 + n0) = u;
-        *reinterpret_cast<tc_f32x4 *>(p.hf_out + cell * 128 + n0 + 4) = v;
-        tc_u32x4 hi, lo;
-        tc_split8(u, v, k2048, hi, lo);
+        for (int e = 0; e < 4; ++e) { u[e] = gru_blend(z0[e], h0[e], fast_tanh(u[e])); v[e] = gru_blend(z1[e], h1[e], fast_tanh(v[e])); }
+        *reinterpret_cast<f32x4 *>(p.hf_out + cell * 128 + n0) = u;
+        *reinterpret_cast<f32x4 *>(p.hf_out + cell * 128 + n0 + 4) = v;
+        u32x4 hi, lo;
+        split8_raw(u, v, k2048, hi, lo);
         uint4 *dst = reinterpret_cast<uint4 *>(reinterpret_cast<char *>(p.h_out + cell * p.ld_hout) + (n0 >> 3) * 32);
         dst[0] = __builtin_bit_cast(uint4, hi);
         dst[1] = __builtin_bit_cast(uint4, lo);
@@ -799,7 +723,7 @@ __global__ __launch_bounds__(512, 2) void ou_head_kernel(OuHeadArgs p) {
     const int x0 = tx_ * TW, y0 = ty_ * TH;
     const long long img_base = (long long)img * p.h * p.w;
     const uint4 *__restrict__ w2 = reinterpret_cast<const uint4 *>(p.wf) + (long long)(wv * OU_PASSES * G::STEPS) * 128 + lane;
-    tc_f32x16 acc[RT], accx[RT];
+    f32x16 acc[RT], accx[RT];
 #pragma unroll
     for (int i = 0; i < RT; ++i)
 #pragma unroll
@@ -819,7 +743,7 @@ __global__ __launch_bounds__(512, 2) void ou_head_kernel(OuHeadArgs p) {
         const uint4 *__restrict__ wp = w2 + (long long)pass * G::STEPS * 128;
 #pragma unroll
         for (int s = 0; s < PF; ++s) { bq[s][0] = wp[s * 128]; bq[s][1] = wp[s * 128 + 64]; }
-        if (pass) tc_barrier();          // every wave is done with the previous pass's channels
+        if (pass) lds_barrier();          // every wave is done with the previous pass's channels
         // ---- channels [144 pass, 144 pass + 144) of the tile (halo included) -> LDS; zeros outside the image and past channel 712
         if constexpr (!GATHER) {
             constexpr int PPC = OU_CP / 4, TOTAL = G::HCELLS * PPC, ROUNDS = (TOTAL + 511) / 512, B = 7;
@@ -856,12 +780,12 @@ __global__ __launch_bounds__(512, 2) void ou_head_kernel(OuHeadArgs p) {
             const float k2048l = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(0x45000000));
 #pragma unroll 1
             for (int rr = 0; rr < ROUNDS; rr += B) {
-                tc_f32x4 v0[B], v1[B];
+                f32x4 v0[B], v1[B];
                 int kind[B];                                   // 0 zeros, 1 split form as is, 2 fp32 to be split
 #pragma unroll
                 for (int k = 0; k < B; ++k) {
                     const int q = (rr + k) * 512 + tid;
-                    v0[k] = tc_f32x4{0.f, 0.f, 0.f, 0.f}; v1[k] = v0[k]; kind[k] = 0;
+                    v0[k] = f32x4{0.f, 0.f, 0.f, 0.f}; v1[k] = v0[k]; kind[k] = 0;
                     if (rr + k < ROUNDS && q < TOTAL) {
                         const int c = q / GPC, gl = q - c * GPC, Gi = GPC * pass + gl;
                         const int cy = c / G::HWD, cx = c - cy * G::HWD;
@@ -870,15 +794,15 @@ __global__ __launch_bounds__(512, 2) void ou_head_kernel(OuHeadArgs p) {
                             const long long cell = img_base + (long long)yy * p.w + xx;
                             if (Gi < 32 || Gi >= 73) {
                                 const float *src = p.hx + cell * 384 + (Gi < 32 ? 8 * Gi : 256 + 8 * (Gi - 73));
-                                v0[k] = *reinterpret_cast<const tc_f32x4 *>(src); v1[k] = *reinterpret_cast<const tc_f32x4 *>(src + 4); kind[k] = 1;
+                                v0[k] = *reinterpret_cast<const f32x4 *>(src); v1[k] = *reinterpret_cast<const f32x4 *>(src + 4); kind[k] = 1;
                             } else if (Gi < 72) {
                                 const float *src = p.corr + cell * p.ld_corr + 8 * (Gi - 32);
-                                v0[k] = *reinterpret_cast<const tc_f32x4 *>(src); v1[k] = *reinterpret_cast<const tc_f32x4 *>(src + 4); kind[k] = 2;
+                                v0[k] = *reinterpret_cast<const f32x4 *>(src); v1[k] = *reinterpret_cast<const f32x4 *>(src + 4); kind[k] = 2;
                             } else {
-                                v0[k] = *reinterpret_cast<const tc_f32x4 *>(p.corr + cell * p.ld_corr + 320);
+                                v0[k] = *reinterpret_cast<const f32x4 *>(p.corr + cell * p.ld_corr + 320);
                                 const float2 cc = reinterpret_cast<const float2 *>(p.coords1)[cell], dd = reinterpret_cast<const float2 *>(p.delta)[cell];
                                 const float fx = cc.x - (float)xx, fy = cc.y - (float)yy;
-                                v1[k] = tc_f32x4{fx, fy, dd.x, dd.y}; kind[k] = 2;
+                                v1[k] = f32x4{fx, fy, dd.x, dd.y}; kind[k] = 2;
                                 if (cy >= 1 && cy <= TH && cx >= 1 && cx <= TW) reinterpret_cast<float2 *>(p.flow_lr)[cell] = make_float2(fx, fy);    // the tile's own cells
                             }
                         }
@@ -889,18 +813,18 @@ __global__ __launch_bounds__(512, 2) void ou_head_kernel(OuHeadArgs p) {
                     const int q = (rr + k) * 512 + tid;
                     if (rr + k < ROUNDS && q < TOTAL) {
                         const int c = q / GPC, gl = q - c * GPC;
-                        tc_u32x4 hi = __builtin_bit_cast(tc_u32x4, v0[k]), lo = __builtin_bit_cast(tc_u32x4, v1[k]);
-                        if (kind[k] == 2) tc_split8(v0[k], v1[k], k2048l, hi, lo);
-                        *reinterpret_cast<tc_u32x4 *>(lds + c * G::CELLB + gl * 32) = hi;
-                        *reinterpret_cast<tc_u32x4 *>(lds + c * G::CELLB + gl * 32 + 16) = lo;
+                        u32x4 hi = __builtin_bit_cast(u32x4, v0[k]), lo = __builtin_bit_cast(u32x4, v1[k]);
+                        if (kind[k] == 2) split8_raw(v0[k], v1[k], k2048l, hi, lo);
+                        *reinterpret_cast<u32x4 *>(lds + c * G::CELLB + gl * 32) = hi;
+                        *reinterpret_cast<u32x4 *>(lds + c * G::CELLB + gl * 32 + 16) = lo;
                     }
                 }
             }
         }
-        tc_barrier();
+        lds_barrier();
         tc_kloop<G, 3>(abase, wp, bq, acc, accx);
     }
-    tc_barrier();           // every wave is done with the input tile: its space takes the sums
+    lds_barrier();           // every wave is done with the input tile: its space takes the sums
 
     // ---- relu(. + bias), parked [cell][256]; then the second layers as the [256 x 27] projection (as TC_RELU_PROJ)
     const float inv2048 = 1.f / 2048.f;
@@ -909,50 +833,50 @@ __global__ __launch_bounds__(512, 2) void ou_head_kernel(OuHeadArgs p) {
     for (int i = 0; i < RT; ++i)
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-            tc_f32x4 v;
+            f32x4 v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = acc[i][4 * b + e] + accx[i][4 * b + e] * inv2048;
-            *reinterpret_cast<tc_f32x4 *>(red + (32 * i + (lane & 31)) * G::RED_ROW + 32 * wv + 8 * b + 4 * (lane >> 5)) = v;
+            *reinterpret_cast<f32x4 *>(red + (32 * i + (lane & 31)) * G::RED_ROW + 32 * wv + 8 * b + 4 * (lane >> 5)) = v;
         }
-    tc_barrier();
+    lds_barrier();
     const float k2048 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(0x45000000));
     const int mt = wv & 3, kh = wv >> 2;
     const uint4 *__restrict__ wpj = reinterpret_cast<const uint4 *>(p.wproj) + lane;
     float *tp = reinterpret_cast<float *>(lds + G::RED_BYTES);
     if (mt < RT) {
-        tc_f32x16 d, dx;
+        f32x16 d, dx;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { d[r] = 0.f; dx[r] = 0.f; }
         const float *xrow = red + (32 * mt + (lane & 31)) * G::RED_ROW + 8 * (lane >> 5);
 #pragma unroll
         for (int gg = 0; gg < 8; ++gg) {
             const int g = 8 * kh + gg;
-            tc_f32x4 u = *reinterpret_cast<const tc_f32x4 *>(xrow + 16 * g), v = *reinterpret_cast<const tc_f32x4 *>(xrow + 16 * g + 4);
-            u += *reinterpret_cast<const tc_f32x4 *>(p.bias + 16 * g + 8 * (lane >> 5));
-            v += *reinterpret_cast<const tc_f32x4 *>(p.bias + 16 * g + 8 * (lane >> 5) + 4);
+            f32x4 u = *reinterpret_cast<const f32x4 *>(xrow + 16 * g), v = *reinterpret_cast<const f32x4 *>(xrow + 16 * g + 4);
+            u += *reinterpret_cast<const f32x4 *>(p.bias + 16 * g + 8 * (lane >> 5));
+            v += *reinterpret_cast<const f32x4 *>(p.bias + 16 * g + 8 * (lane >> 5) + 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { u[e] = relu_keep_nan(u[e]); v[e] = relu_keep_nan(v[e]); }
-            tc_u32x4 hi, lo;
-            tc_split8(u, v, k2048, hi, lo);
-            const tc_f16x8 wh = __builtin_bit_cast(tc_f16x8, wpj[(g * 2) * 64]), wl = __builtin_bit_cast(tc_f16x8, wpj[(g * 2 + 1) * 64]);
+            u32x4 hi, lo;
+            split8_raw(u, v, k2048, hi, lo);
+            const f16x8 wh = __builtin_bit_cast(f16x8, wpj[(g * 2) * 64]), wl = __builtin_bit_cast(f16x8, wpj[(g * 2 + 1) * 64]);
             asm volatile("s_nop 1" : "+v"(hi), "+v"(lo));
-            const tc_f16x8 xh = __builtin_bit_cast(tc_f16x8, hi), xl = __builtin_bit_cast(tc_f16x8, lo);
-            d = tc_mfma(wh, xh, d);
-            dx = tc_mfma(wl, xh, dx);
-            dx = tc_mfma(wh, xl, dx);
+            const f16x8 xh = __builtin_bit_cast(f16x8, hi), xl = __builtin_bit_cast(f16x8, lo);
+            d = mfma_f16(wh, xh, d);
+            dx = mfma_f16(wl, xh, dx);
+            dx = mfma_f16(wh, xl, dx);
         }
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const int j0 = 8 * b + 4 * (lane >> 5);          // this lane's outputs j0 .. j0 + 3 of cell 32 mt + (lane & 31); 27 exist
             if (j0 < OU_PROJ_ROW) {
-                tc_f32x4 v;
+                f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = d[4 * b + e] + dx[4 * b + e] * inv2048;
-                *reinterpret_cast<tc_f32x4 *>(tp + (kh * CELLS + 32 * mt + (lane & 31)) * OU_PROJ_ROW + j0) = v;
+                *reinterpret_cast<f32x4 *>(tp + (kh * CELLS + 32 * mt + (lane & 31)) * OU_PROJ_ROW + j0) = v;
             }
         }
     }
-    tc_barrier();
+    lds_barrier();
     for (int idx = tid; idx < CELLS * 27; idx += 512) {
         const int m = idx / 27, j = idx - m * 27;
         const int yy = y0 + m / TW, xx = x0 + m % TW;
@@ -1253,7 +1177,7 @@ __device__ __forceinline__ void tc2p_main(const TileConv2pArgs &p, unsigned char
                                           float *slab, int rowf, int col0) {
     constexpr int RT = G::RT, PF = 3, PASSES = 2;
     const int tid = (int)threadIdx.x, lane = tid & 63;
-    tc_f32x16 acc[RT], accx[RT];
+    f32x16 acc[RT], accx[RT];
 #pragma unroll
     for (int i = 0; i < RT; ++i)
 #pragma unroll
@@ -1273,7 +1197,7 @@ __device__ __forceinline__ void tc2p_main(const TileConv2pArgs &p, unsigned char
         uint4 bq[PF][2];
 #pragma unroll
         for (int s = 0; s < PF; ++s) { bq[s][0] = wp[s * 128]; bq[s][1] = wp[s * 128 + 64]; }      // in flight while the tile loads
-        if (pass) tc_barrier();          // every wave is done with the first pass's channels
+        if (pass) lds_barrier();          // every wave is done with the first pass's channels
         // ---- channels [128 pass, 128 pass + 128) of the tile (halo included) -> LDS, 16-byte pieces, zeros outside the image
         {
             constexpr int PPC = 32, TOTAL = G::HCELLS * PPC, ROUNDS = (TOTAL + 511) / 512, B = 8;
@@ -1302,19 +1226,19 @@ __device__ __forceinline__ void tc2p_main(const TileConv2pArgs &p, unsigned char
                 }
             }
         }
-        tc_barrier();
+        lds_barrier();
         tc_kloop<G, 3>(abase, wp, bq, acc, accx);
     }
-    tc_barrier();           // every wave is done with the input tile: its space takes the sums
+    lds_barrier();           // every wave is done with the input tile: its space takes the sums
     const float inv2048 = 1.f / 2048.f;
 #pragma unroll
     for (int i = 0; i < RT; ++i)
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-            tc_f32x4 v;
+            f32x4 v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = acc[i][4 * b + e] + accx[i][4 * b + e] * inv2048;
-            *reinterpret_cast<tc_f32x4 *>(slab + (32 * i + (lane & 31)) * rowf + col0 + 8 * b + 4 * (lane >> 5)) = v;
+            *reinterpret_cast<f32x4 *>(slab + (32 * i + (lane & 31)) * rowf + col0 + 8 * b + 4 * (lane >> 5)) = v;
         }
 }
 
@@ -1347,7 +1271,7 @@ __global__ __launch_bounds__(512, 2) void tile_conv2p_kernel(TileConv2pArgs p) {
     const int col0 = second && N == 192 ? 32 * (nt - 4) : 32 * nt;
     if (N == 192 && full) tc2p_main<GF, TH, TW>(p, lds, w2, 0, x0, y0, img_base, slab, rowf, col0);
     else tc2p_main<GH, TH, TW>(p, lds, w2, ks * 64, x0, y0, img_base, slab, rowf, col0);
-    tc_barrier();
+    lds_barrier();
 
     // ---- row-wise epilogue: 8 consecutive channels of a cell per lane
     const float k2048 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(0x45000000));
@@ -1359,26 +1283,26 @@ __global__ __launch_bounds__(512, 2) void tile_conv2p_kernel(TileConv2pArgs p) {
         const int m = item / GPC, n0 = (item % GPC) * 8;
         const int yy = y0 + m / TW, xx = x0 + m % TW;
         const float *src = red + m * RED0 + n0;
-        tc_f32x4 u = *reinterpret_cast<const tc_f32x4 *>(src), v = *reinterpret_cast<const tc_f32x4 *>(src + 4);
+        f32x4 u = *reinterpret_cast<const f32x4 *>(src), v = *reinterpret_cast<const f32x4 *>(src + 4);
         if (N == 128 || n0 >= 128) {
             const float *s1 = red + CELLS * RED0 + m * RED1 + (N == 128 ? n0 : n0 - 128);
-            u += *reinterpret_cast<const tc_f32x4 *>(s1);
-            v += *reinterpret_cast<const tc_f32x4 *>(s1 + 4);
+            u += *reinterpret_cast<const f32x4 *>(s1);
+            v += *reinterpret_cast<const f32x4 *>(s1 + 4);
         }
         if (yy >= p.h || xx >= p.w || n0 >= p.n_valid) continue;
         const long long cell = img_base + (long long)yy * p.w + xx;
         const int nv = p.n_valid - n0;                  // channels of this group that exist (>= 8: all)
         if (nv >= 8) {
-            u += *reinterpret_cast<const tc_f32x4 *>(p.bias + n0);
-            v += *reinterpret_cast<const tc_f32x4 *>(p.bias + n0 + 4);
+            u += *reinterpret_cast<const f32x4 *>(p.bias + n0);
+            v += *reinterpret_cast<const f32x4 *>(p.bias + n0 + 4);
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) { if (e < nv) u[e] += p.bias[n0 + e]; if (4 + e < nv) v[e] += p.bias[n0 + 4 + e]; }
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) { u[e] = relu_keep_nan(u[e]); v[e] = relu_keep_nan(v[e]); }
-        tc_u32x4 hi, lo;
-        tc_split8(u, v, k2048, hi, lo);
+        u32x4 hi, lo;
+        split8_raw(u, v, k2048, hi, lo);
         unsigned *dst = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(p.out + cell * p.ldo) + (n0 >> 3) * 32);
         if (nv >= 8) {
             reinterpret_cast<uint4 *>(dst)[0] = __builtin_bit_cast(uint4, hi);

@@ -16,14 +16,9 @@
 // multiplies.
 #include "common.h"
 #include "profile.h"
+#include "device_prims.h"
 
 namespace mftx {
-
-typedef float vt_f32x16 __attribute__((ext_vector_type(16)));
-typedef float vt_f32x4 __attribute__((ext_vector_type(4)));
-typedef float vt_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned vt_u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 vt_f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int VT_C = 256;                       // feature channels
 constexpr int VT_ROW = VT_C * 4 + 16;           // bytes per resident target row (consecutive targets 65 sixteen-byte slots apart)
@@ -44,42 +39,6 @@ struct VolTileArgs {
     PairPtrs f1p;
 };
 
-__device__ __forceinline__ vt_f32x16 vt_mfma(const vt_f16x8 &a, const vt_f16x8 &b, const vt_f32x16 &c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-// hi / lo halves of 8 consecutive k (conv_gemm.hip: split8); ends with the two wait states an MFMA needs behind a VALU write
-__device__ __forceinline__ void vt_split8(const vt_f32x4 &u, const vt_f32x4 &v, float k2048, vt_f16x8 &hi, vt_f16x8 &lo) {
-    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-    float r0, r1, r2, r3, r4, r5, r6, r7;
-    asm("v_cvt_pk_f16_f32 %0, %16, %17\n\t"
-        "v_cvt_pk_f16_f32 %1, %18, %19\n\t"
-        "v_cvt_pk_f16_f32 %2, %20, %21\n\t"
-        "v_cvt_pk_f16_f32 %3, %22, %23\n\t"
-        "v_fma_mix_f32 %8, %0, -1.0, %16 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %9, %0, -1.0, %17 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %10, %1, -1.0, %18 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %11, %1, -1.0, %19 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %12, %2, -1.0, %20 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %13, %2, -1.0, %21 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %14, %3, -1.0, %22 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %15, %3, -1.0, %23 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixlo_f16 %4, %8, %24, 0\n\t"
-        "v_fma_mixlo_f16 %5, %10, %24, 0\n\t"
-        "v_fma_mixlo_f16 %6, %12, %24, 0\n\t"
-        "v_fma_mixlo_f16 %7, %14, %24, 0\n\t"
-        "v_fma_mixhi_f16 %4, %9, %24, 0\n\t"
-        "v_fma_mixhi_f16 %5, %11, %24, 0\n\t"
-        "v_fma_mixhi_f16 %6, %13, %24, 0\n\t"
-        "v_fma_mixhi_f16 %7, %15, %24, 0\n\t"
-        "s_nop 1"
-        : "=&v"(h0), "=&v"(h1), "=&v"(h2), "=&v"(h3), "=&v"(l0), "=&v"(l1), "=&v"(l2), "=&v"(l3),
-          "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5), "=&v"(r6), "=&v"(r7)
-        : "v"(u[0]), "v"(u[1]), "v"(u[2]), "v"(u[3]), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "s"(k2048));
-    hi = __builtin_bit_cast(vt_f16x8, vt_u32x4{h0, h1, h2, h3});
-    lo = __builtin_bit_cast(vt_f16x8, vt_u32x4{l0, l1, l2, l3});
-}
-
 // lane i <- lane i + N (row_shl) / lane i - N (row_shr) inside its row of 16 lanes; lanes without a source read 0
 template <int N>
 __device__ __forceinline__ float vt_shl(float v) {
@@ -90,12 +49,9 @@ __device__ __forceinline__ float vt_shr(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x110 + N, 0xf, 0xf, true));
 }
 
-// ATen's avg_pool2d order: ((a + b) + c + d) * 0.25, a b = top row, c d = bottom row
-__device__ __forceinline__ float vt_pool4(float a, float b, float c, float d) { return (((a + b) + c) + d) * 0.25f; }
-
 // QSPLIT: the query features arrive in split form (mftx_raft_frame_prepare: a frame is the query map of up to seven later
 // pairs) -- a k group's two 16-byte loads ARE the hi x 8 and lo x 8 halves, nothing is split in the K loop.  The same halves
-// (launch_split_weights and vt_split8 round the same way, value for value), the same MFMAs: the same bits.
+// (launch_split_weights and split8 round the same way, value for value), the same MFMAs: the same bits.
 template <bool QSPLIT>
 __global__ __launch_bounds__(512, 2) void volume_tile_kernel(VolTileArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char vt_lds[];
@@ -119,9 +75,7 @@ __global__ __launch_bounds__(512, 2) void volume_tile_kernel(VolTileArgs p) {
             *reinterpret_cast<uint4 *>(lds + m * VT_ROW + pc * 16) = v;
         }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (no implicit wait in front of s_barrier on gfx950: tile_conv.hip, tc_barrier)
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    lds_barrier();
 
     const unsigned char *abase = lds + (lane & 31) * VT_ROW + (lane >> 5) * 32;      // + 32 j rows, + 64 g
     const int n_blocks = (p.N + 31) >> 5;
@@ -137,7 +91,7 @@ __global__ __launch_bounds__(512, 2) void volume_tile_kernel(VolTileArgs p) {
     const int l1_src = 4 * (32 * hf + 2 * (pp & 3) + 16 * ((pp >> 3) & 1) + ((pp >> 2) & 1) + 8 * (pp >> 4));
     const int l3_src = 4 * ((lane + 16) & 63);
     constexpr int PF = 3;
-    vt_f32x4 raw[PF][2];
+    f32x4 raw[PF][2];
     const float *f1base = p.gathered ? p.f1p.p[bz] : p.f1 + qbase * VT_C;
     auto row_of = [&](int qb) {
         const int q = qb * 32 + (lane & 31);
@@ -146,51 +100,51 @@ __global__ __launch_bounds__(512, 2) void volume_tile_kernel(VolTileArgs p) {
     auto prefetch = [&](const float *src) {
 #pragma unroll
         for (int g = 0; g < PF; ++g) {
-            raw[g][0] = *reinterpret_cast<const vt_f32x4 *>(src + 16 * g);
-            raw[g][1] = *reinterpret_cast<const vt_f32x4 *>(src + 16 * g + 4);
+            raw[g][0] = *reinterpret_cast<const f32x4 *>(src + 16 * g);
+            raw[g][1] = *reinterpret_cast<const f32x4 *>(src + 16 * g + 4);
         }
     };
     if (b_lo + wv < b_hi) prefetch(row_of(b_lo + wv));
     for (int qb = b_lo + wv; qb < b_hi; qb += 8) {
         const float *src = row_of(qb);
-        vt_f32x16 acc[4], accx[4];
+        f32x16 acc[4], accx[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) { acc[j][r] = 0.f; accx[j][r] = 0.f; }
-        vt_f16x8 ah[2][4], al[2][4];
+        f16x8 ah[2][4], al[2][4];
         auto read_a = [&](int g, int set) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                ah[set][j] = *reinterpret_cast<const vt_f16x8 *>(abase + j * 32 * VT_ROW + g * 64);
-                al[set][j] = *reinterpret_cast<const vt_f16x8 *>(abase + j * 32 * VT_ROW + g * 64 + 16);
+                ah[set][j] = *reinterpret_cast<const f16x8 *>(abase + j * 32 * VT_ROW + g * 64);
+                al[set][j] = *reinterpret_cast<const f16x8 *>(abase + j * 32 * VT_ROW + g * 64 + 16);
             }
         };
         read_a(0, 0);
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
             const int set = g & 1;
-            vt_f16x8 bh, bl;
+            f16x8 bh, bl;
             if constexpr (QSPLIT) {
-                bh = __builtin_bit_cast(vt_f16x8, raw[g % PF][0]);
-                bl = __builtin_bit_cast(vt_f16x8, raw[g % PF][1]);
-            } else vt_split8(raw[g % PF][0], raw[g % PF][1], k2048, bh, bl);
+                bh = __builtin_bit_cast(f16x8, raw[g % PF][0]);
+                bl = __builtin_bit_cast(f16x8, raw[g % PF][1]);
+            } else split8(raw[g % PF][0], raw[g % PF][1], k2048, bh, bl);
             __builtin_amdgcn_sched_barrier(0);
             if (g + 1 < 16) read_a(g + 1, set ^ 1);
             if (g + PF < 16) {
-                raw[g % PF][0] = *reinterpret_cast<const vt_f32x4 *>(src + 16 * (g + PF));
-                raw[g % PF][1] = *reinterpret_cast<const vt_f32x4 *>(src + 16 * (g + PF) + 4);
+                raw[g % PF][0] = *reinterpret_cast<const f32x4 *>(src + 16 * (g + PF));
+                raw[g % PF][1] = *reinterpret_cast<const f32x4 *>(src + 16 * (g + PF) + 4);
             }
             __builtin_amdgcn_sched_barrier(0);
             // (queries first: D = f1_block x f2_tile^T, queries x targets -- a lane holds ONE target cell of each block for 16 queries)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = vt_mfma(bh, ah[set][j], acc[j]);
+            for (int j = 0; j < 4; ++j) acc[j] = mfma_f16(bh, ah[set][j], acc[j]);
             // (cross terms in the ring-buffered kernel's order -- query hi x target lo, then query lo x target hi: the same sequence
             // of products and sums per output, the same bits)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) accx[j] = vt_mfma(bh, al[set][j], accx[j]);
+            for (int j = 0; j < 4; ++j) accx[j] = mfma_f16(bh, al[set][j], accx[j]);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) accx[j] = vt_mfma(bl, ah[set][j], accx[j]);
+            for (int j = 0; j < 4; ++j) accx[j] = mfma_f16(bl, ah[set][j], accx[j]);
             __builtin_amdgcn_sched_barrier(0);
         }
 
@@ -256,17 +210,17 @@ __global__ __launch_bounds__(512, 2) void volume_tile_kernel(VolTileArgs p) {
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) vv[i][j] = (acc[j][4 * g + i] + accx[j][4 * g + i] * inv2048) * p.scale;
-            vt_f32x4 line[4];
+            f32x4 line[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) slab[(4 * hf + i) * 32 + m] = vv[i][j];
-                line[j] = *reinterpret_cast<const vt_f32x4 *>(slab + (le >> 3) * 32 + (le & 7) * 4);
+                line[j] = *reinterpret_cast<const f32x4 *>(slab + (le >> 3) * 32 + (le & 7) * 4);
             }
             if (st0g) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(vt_u32x4, line[j]), r0, v0off4 + (j >> 1) * jrow + (j & 1) * 128u, (unsigned)(8 * g) * s0b, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, line[j]), r0, v0off4 + (j >> 1) * jrow + (j & 1) * 128u, (unsigned)(8 * g) * s0b, 0);
             }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -348,15 +302,15 @@ static int vt_num_cus() {
 
 bool volume_tile_applicable(int C) { return C == VT_C; }
 
-// a row of raw fp32 features -> its split form through vt_split8 itself (mftx_volume_query_split: the tests compare it with
+// a row of raw fp32 features -> its split form through split8 itself (mftx_volume_query_split: the tests compare it with
 // launch_split_weights, value for value)
 __global__ void vt_query_split_kernel(const float *__restrict__ in, uint4 *__restrict__ out, long long n8) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const float k2048 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(0x45000000));
     if (i >= n8) return;
-    const vt_f32x4 u = *reinterpret_cast<const vt_f32x4 *>(in + i * 8), v = *reinterpret_cast<const vt_f32x4 *>(in + i * 8 + 4);
-    vt_f16x8 hi, lo;
-    vt_split8(u, v, k2048, hi, lo);
+    const f32x4 u = *reinterpret_cast<const f32x4 *>(in + i * 8), v = *reinterpret_cast<const f32x4 *>(in + i * 8 + 4);
+    f16x8 hi, lo;
+    split8(u, v, k2048, hi, lo);
     out[2 * i] = __builtin_bit_cast(uint4, hi);
     out[2 * i + 1] = __builtin_bit_cast(uint4, lo);
 }

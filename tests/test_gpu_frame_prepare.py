@@ -2,7 +2,7 @@
 gate sums and the split form of the feature map, handed to ``mftx_raft_refine_gather_ex`` instead of being recomputed in every pair.
 
 A. The split map: ``mftx_split_weights`` (what the prepare call runs) equals the register split of the tile-resident volume kernel's
-   query loads (``mftx_volume_query_split``: vt_split8 itself) value for value -- also at the edges of the fp16 range.
+   query loads (``mftx_volume_query_split``: split8 itself) value for value -- also at the edges of the fp16 range.
 B. The engine: ``refine`` with and without the prepared parts, bit for bit, before and after graph capture, with the pointers changing
    from call to call.
 C. The tracker: 40 frames with ``frame_prepare`` on and off, bit for bit, ramp-up frames included, one and two frames in flight.
@@ -26,7 +26,7 @@ def _bits(t):
 # =====================================================================================================================
 
 def test_prepared_split_map_equals_volume_register_split():
-    """Every 8 floats -> [hi x 8 | lo x 8]: the standalone split kernel and vt_split8 give the same 32 bytes for feature-like values,
+    """Every 8 floats -> [hi x 8 | lo x 8]: the standalone split kernel and split8 give the same 32 bytes for feature-like values,
     for values whose low half is subnormal or zero, for the largest operands of the split arithmetic, and for zeros of both signs."""
     from mft_amd import ops, _lib
     lib = _lib.load()

@@ -394,17 +394,20 @@ def test_point_tracking_adapter():
 def test_every_raw_s_barrier_is_preceded_by_an_lds_wait():
     """gfx950 has back-off barriers: the compiler inserts no s_waitcnt in front of s_barrier and __builtin_amdgcn_s_barrier() is no
     fence, so a hand-written barrier must wait for its wave's LDS operations itself (round 5: the race behind
-    tests/test_gpu_contention.py).  Source-level guard: every raw s_barrier in csrc/ has `s_waitcnt lgkmcnt(0)` just in front."""
+    tests/test_gpu_contention.py).  Source-level guard: every raw s_barrier in csrc/ has `s_waitcnt lgkmcnt(0)` just in front --
+    and there is exactly one, device_prims.h's lds_barrier(), which every kernel calls."""
     import re
-    bad = []
+    bad, found = [], []
     for path in sorted((REPO / "mft_amd" / "csrc").glob("*.h*")):
         lines = path.read_text().splitlines()
         for i, line in enumerate(lines):
             if "__builtin_amdgcn_s_barrier()" in line and not line.lstrip().startswith("//"):
+                found.append(path.name)
                 before = "\n".join(lines[max(0, i - 3): i])
                 if not re.search(r's_waitcnt lgkmcnt\(0\)', before):
                     bad.append(f"{path.name}:{i + 1}")
     assert not bad, bad
+    assert found == ["device_prims.h"], found
 
 
 def test_chain_kernels_are_built_without_packed_fp32_code():
