@@ -332,6 +332,21 @@ int mftx_raft_set_coords_trace(mftx_raft *r, float *trace);
 #define MFTX_RAFT_OPT_FUSE_OU 11
 #define MFTX_RAFT_OPT_TILE_CONV2P 12
 int mftx_raft_set_option(mftx_raft *r, int option, int value);
+/* The launch schedule mftx_raft_refine* would run for P pairs of h x w cells with the handle as it stands (its options, arithmetic,
+ * weight streams, coords trace, the profiler): every decision that is constant over a call, as MFTX_RAFT_PLAN_FIELDS ints in out
+ * (n = MFTX_RAFT_PLAN_FIELDS).  ctx_supplied: the call brings prepared context parts (mftx_raft_refine_gather_ex).  Launches
+ * nothing, needs no device (without one the chip is taken to have 256 CUs, as an MI355X has).  In this order:
+ *   presplit, fuse_lookup, tiles_on (the tile-resident layers run), gru_fused, ctx_supplied (the prepared parts are honoured),
+ *   two_pass (convc2 / conv tile-resident), flow (MFTX_FLOW_*: where the motion encoder's flow branch goes), pair_second (convc2 +
+ *   convf2 as one launch), head_fused, defer_update (a non-last coordinate update is left to the next flow-branch kernel), ou_fused,
+ *   ou_materialised (the OU heads' input is gathered into the workspace), use_graph, side_stream (created ahead of a capture) */
+#define MFTX_RAFT_PLAN_FIELDS 14
+#define MFTX_FLOW_FUSED 0         /* one kernel (mftx_flow_branch), in front of the correlation branch */
+#define MFTX_FLOW_SIDE 1          /* convf1, convf2 on the handle's side stream beside the correlation branch */
+#define MFTX_FLOW_FIRST 2         /* convf1, convf2, then the correlation branch, on one stream */
+#define MFTX_FLOW_AFTER_LOOKUP 3  /* lookup, convf1 as a launch of its own, convc1, convc2, convf2 */
+#define MFTX_FLOW_WITH_LOOKUP 4   /* lookup + convf1 as one launch, convc1, convc2, convf2 */
+int mftx_raft_plan(const mftx_raft *r, int P, int h, int w, int ctx_supplied, int *out, int n);
 /* A device-resident counter (4 bytes, zeroed by the caller) that the last kernel of every mftx_raft_refine* call increments
  * by the number of output pixels with a non-finite flow / occlusion / sigma; null switches it off.  The reference has no
  * such check (MFT/MFT.py:96-107 stores whatever the network returned): with the split arithmetic an activation beyond

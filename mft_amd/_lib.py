@@ -70,6 +70,7 @@ SIGNATURES = {
     "mftx_flow_branch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "mftx_raft_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "mftx_raft_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "mftx_raft_set_coords_trace": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mftx_gru_half": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -190,29 +190,32 @@ static Workspace carve(void *base, int P, int h, int w, bool ondemand = false, b
 
 using namespace mftx;
 
+static constexpr uint32_t RAFT_MAGIC = 0x4d465458;  // "MFTX"
 struct mftx_raft {
-    uint32_t magic;
-    int ondemand;                  // 1: on-demand correlation (no volume), see csrc/corr_ondemand.hip
-    int arith;                     // MFTX_ARITH_*: arithmetic of the update block's matrix products
-    const float *w[W_COUNT];
-    const float *wg[W_COUNT];      // what the GEMM layers stream: w, or the split form of it (arith = MFTX_ARITH_SPLIT)
+    uint32_t magic = RAFT_MAGIC;
+    int ondemand = 0;              // 1: on-demand correlation (no volume), see csrc/corr_ondemand.hip
+    int arith = MFTX_ARITH_F32;    // MFTX_ARITH_*: arithmetic of the update block's matrix products
+    const float *w[W_COUNT] = {};
+    const float *wg[W_COUNT] = {}; // what the GEMM layers stream: w, or the split form of it (arith = MFTX_ARITH_SPLIT)
     // the motion encoder's flow branch (convf1 -> convf2) runs on a stream of its own, beside lookup -> convc1 -> convc2
-    hipStream_t side;
-    hipEvent_t ev_fork, ev_join;
-    float *coords_trace;           // debug payload (mftx_raft_set_coords_trace): coords1 before every iteration and after the last, or null
-    GraphCache *graphs;            // the refinement's launch sequence between its first and last kernels, captured per (shape, workspace, mode)
-    const void *wfused;            // convc1's weights for the fused lookup + convc1 kernel (csrc/lookup_convc1.hip), or null
-    const void *wflow;             // convf1's and convf2's weights for the fused flow-branch kernel (csrc/flow_branch.hip), or null
-    const void *wproj;             // the flow head's last layer as the projection epilogue of its first (csrc/tile_conv.hip: TC_RELU_PROJ), or null
-    const void *wt[W_COUNT];       // weight streams of the tile-resident conv kernel (csrc/tile_conv.hip) per slot, or null
-    const void *wou, *wouproj;     // the occlusion + uncertainty heads as one tile-resident kernel (csrc/tile_conv.hip: ou_head_kernel), or null
-    int opt[13];                   // MFTX_RAFT_OPT_*
-    unsigned *nonfinite;           // device counter of non-finite output pixels (mftx_raft_set_nonfinite_counter), or null
+    hipStream_t side = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    float *coords_trace = nullptr; // debug payload (mftx_raft_set_coords_trace): coords1 before every iteration and after the last, or null
+    GraphCache *graphs = nullptr;  // the refinement's launch sequence between its first and last kernels, captured per (shape, workspace, mode)
+    const void *wfused = nullptr;  // convc1's weights for the fused lookup + convc1 kernel (csrc/lookup_convc1.hip), or null
+    const void *wflow = nullptr;   // convf1's and convf2's weights for the fused flow-branch kernel (csrc/flow_branch.hip), or null
+    const void *wproj = nullptr;   // the flow head's last layer as the projection epilogue of its first (csrc/tile_conv.hip: TC_RELU_PROJ), or null
+    const void *wt[W_COUNT] = {};  // weight streams of the tile-resident conv kernel (csrc/tile_conv.hip) per slot, or null
+    const void *wou = nullptr, *wouproj = nullptr;     // the occlusion + uncertainty heads as one tile-resident kernel (csrc/tile_conv.hip: ou_head_kernel), or null
+    // MFTX_RAFT_OPT_*, in the order of their numbers: the defaults documented in include/mftx.h
+    int opt[13] = {/* FORK */ -1, /* PRESPLIT */ 1, /* GROUP */ 1, /* FUSE_LOOKUP */ 1, /* GRAPH */ 1, /* FUSE_FLOW */ 1, /* TILE_CONV */ 1,
+                   /* FUSE_HEAD */ 1, /* TILE_VOLUME */ 1, /* FUSE_GRU */ 1, /* TILE_CELLS */ 0, /* FUSE_OU */ 1, /* TILE_CONV2P */ 1};
+    unsigned *nonfinite = nullptr; // device counter of non-finite output pixels (mftx_raft_set_nonfinite_counter), or null
 };
+static_assert(MFTX_RAFT_OPT_TILE_CONV2P == 12, "mftx_raft::opt lists one default per option");
 // weights that go through the conv GEMM (the others feed VALU kernels and stay fp32)
 static constexpr int GEMM_SLOTS[] = {W_CONVC1, W_CONVC2, W_CONVF2, W_CONV, W_ZR1_DYN, W_ZR1_INP, W_Q1_DYN, W_Q1_INP,
                                      W_ZR2_DYN, W_ZR2_INP, W_Q2_DYN, W_Q2_INP, W_FH1, W_MASK0, W_MASK2, W_OU1};
-static constexpr uint32_t RAFT_MAGIC = 0x4d465458;  // "MFTX"
 
 extern "C" int mftx_raft_create(const float *const *weights, int n_weights, mftx_raft **out) {
     if (!weights || !out) return fail(MFTX_E_ARG, "raft_create: null pointer");
@@ -223,19 +226,7 @@ extern "C" int mftx_raft_create(const float *const *weights, int n_weights, mftx
     }
     mftx_raft *r = new (std::nothrow) mftx_raft;
     if (!r) return fail(MFTX_E_ARG, "raft_create: out of host memory");
-    r->magic = RAFT_MAGIC;
-    r->ondemand = 0;
-    r->arith = MFTX_ARITH_F32;
-    r->side = nullptr; r->ev_fork = nullptr; r->ev_join = nullptr;
-    r->wfused = nullptr;
-    r->wflow = nullptr;
-    r->wproj = nullptr;
-    r->wou = nullptr; r->wouproj = nullptr;
-    for (int i = 0; i < W_COUNT; ++i) r->wt[i] = nullptr;
-    r->coords_trace = nullptr;
-    r->nonfinite = nullptr;
     r->graphs = new (std::nothrow) GraphCache;
-    r->opt[MFTX_RAFT_OPT_FORK] = -1; r->opt[MFTX_RAFT_OPT_PRESPLIT] = 1; r->opt[MFTX_RAFT_OPT_GROUP] = 1; r->opt[MFTX_RAFT_OPT_FUSE_LOOKUP] = 1; r->opt[MFTX_RAFT_OPT_GRAPH] = 1; r->opt[MFTX_RAFT_OPT_FUSE_FLOW] = 1; r->opt[MFTX_RAFT_OPT_TILE_CONV] = 1; r->opt[MFTX_RAFT_OPT_FUSE_HEAD] = 1; r->opt[MFTX_RAFT_OPT_TILE_VOLUME] = 1; r->opt[MFTX_RAFT_OPT_FUSE_GRU] = 1; r->opt[MFTX_RAFT_OPT_TILE_CELLS] = 0; r->opt[MFTX_RAFT_OPT_FUSE_OU] = 1; r->opt[MFTX_RAFT_OPT_TILE_CONV2P] = 1;
     for (int i = 0; i < W_COUNT; ++i) r->w[i] = r->wg[i] = weights[i];
     *out = r;
     return 0;
@@ -395,16 +386,78 @@ extern "C" int mftx_raft_workspace_layout_for(const mftx_raft *r, int P, int h, 
 
 #define TRY(expr) do { int _e = (expr); if (_e) return _e; } while (0)
 
-static mftx_conv_desc conv_desc(const float *a0, int lda0, int c0, const float *a1, int lda1, int c1,
-                                const float *w, const float *b, float *out, int ldo, int P, int h, int wd, int N,
-                                int kh, int kw, int act, float scale = 1.f, const float *addend = nullptr,
-                                int ld_addend = 0) {
-    mftx_conv_desc d{};
-    d.addend = addend; d.ld_addend = ld_addend;
-    d.a0 = a0; d.lda0 = lda0; d.c0 = c0; d.a1 = a1; d.lda1 = lda1; d.c1 = c1;
-    d.wpk = w; d.bias = b; d.out = out; d.ldo = ldo; d.P = P; d.h = h; d.w = wd; d.N = N;
-    d.kh = kh; d.kw = kw; d.act = act; d.out_scale = scale;
-    return d;
+// ---- the launch schedule of a refinement: decided once per call (RefinePlan), then run (RefineCall) ----
+// The motion encoder has two independent branches (core/update.py:152-158): correlation lookup -> convc1 -> convc2 and
+// convf1 -> convf2 on the flow.  Both need only coords1.  Where the flow branch goes (measurements: DESIGN.md "Grouped launches"):
+enum FlowSchedule { FLOW_FUSED = MFTX_FLOW_FUSED, FLOW_SIDE = MFTX_FLOW_SIDE, FLOW_FIRST = MFTX_FLOW_FIRST, FLOW_AFTER_LOOKUP = MFTX_FLOW_AFTER_LOOKUP,
+                    FLOW_WITH_LOOKUP = MFTX_FLOW_WITH_LOOKUP };       // (each described next to its number in include/mftx.h)
+
+// Every decision that is constant over a call, in mftx_raft_plan's order.  Dynamic inside the loop: "the last iteration" and Coords.
+struct RefinePlan {
+    bool SP, fuse_lookup, tiles_on, gru_fused, ctx_supplied, two_pass;
+    FlowSchedule flow;
+    bool pair_second;        // FLOW_AFTER_LOOKUP / FLOW_WITH_LOOKUP: convc2 + convf2 as one launch (launch_conv_pair)
+    bool head_fused, defer_update, ou_fused, ou_materialised, use_graph, side_stream;
+};
+
+// prof: the per-kernel timing pass (everything in order, one launch per kernel); trace: a coords trace is set
+static RefinePlan refine_plan(const mftx_raft &r, int P, int h, int w, bool gather_has_ctx, bool prof, bool trace) {
+    const int *opt = r.opt;
+    const bool split = r.arith == MFTX_ARITH_SPLIT, ondemand = r.ondemand != 0;
+    RefinePlan p{};
+    // split arithmetic: every tensor that feeds a GEMM of the update block / OU heads lives in the workspace in SPLIT
+    // form (common.h), written that way by its producer -- the GEMMs' K loops then spend nothing on splitting
+    p.SP = split && opt[MFTX_RAFT_OPT_PRESPLIT] != 0;
+    // lookup fused into convc1 (csrc/lookup_convc1.hip): the 324 features stay in LDS; they are materialised on the last
+    // iteration only, for the occlusion / uncertainty heads
+    p.fuse_lookup = p.SP && !ondemand && r.wfused != nullptr && opt[MFTX_RAFT_OPT_FUSE_LOOKUP] != 0 && lookup_convc1_applicable(P, h, w, 256);
+    // Layers whose input tile fits a CU's LDS run on the tile-resident kernel (csrc/tile_conv.hip) when its weight streams are set (option value
+    // 2: whatever the batch; 1, the default: only when the tiles fill the chip -- at 256 x 256 pixels or one pair per GPU the ring-buffered kernel wins)
+    p.tiles_on = p.SP && opt[MFTX_RAFT_OPT_TILE_CONV] != 0 && (opt[MFTX_RAFT_OPT_TILE_CONV] == 2 ||
+                 (tile_conv_fills_chip(P, h, w, 3, 3) && tile_conv_fills_chip(P, h, w, 1, 5) && tile_conv_fills_chip(P, h, w, 5, 1)));
+    auto tile_w = [&](int slot) { return p.tiles_on && r.wt[slot] != nullptr; };
+    // SepConvGRU as one kernel per pass, decided ONCE for both passes: they hand h over through the ping-pong pair hx/hf <-> hb/hfb, so one
+    // fused and one unfused pass would read a buffer the other never wrote -- a partial set of tile weights runs both passes unfused
+    p.gru_fused = tile_w(W_ZR1_DYN) && tile_w(W_Q1_DYN) && tile_w(W_ZR2_DYN) && tile_w(W_Q2_DYN) && opt[MFTX_RAFT_OPT_FUSE_GRU] != 0;
+    // context parts that came with the pairs are honoured where the fused pass reads them through the table; elsewhere computed here as ever
+    p.ctx_supplied = gather_has_ctx && p.gru_fused;
+    // convc2 and conv (3 x 3 over 256 channels): tile-resident in two channel passes where the tile-resident layers run (round 6)
+    p.two_pass = p.tiles_on && opt[MFTX_RAFT_OPT_TILE_CONV2P] != 0 && r.wt[W_CONVC2] && r.wt[W_CONV];
+    // MFTX_RAFT_OPT_GROUP = 0 and the timing pass run everything in order, one launch per layer; fp32 MFMA keeps round 1's
+    // grouping (lookup + convf1 in one launch, convc2 + convf2 in one launch) and is never forked; MFTX_RAFT_OPT_FORK = 0 / 2: in
+    // order on one stream, 2 with the flow branch first (with the fused lookup only)
+    const bool grouped = opt[MFTX_RAFT_OPT_GROUP] != 0;
+    const int fork = opt[MFTX_RAFT_OPT_FORK];
+    const bool fuse_flow = p.SP && r.wflow != nullptr && opt[MFTX_RAFT_OPT_FUSE_FLOW] != 0 && grouped;
+    const bool serial = fuse_flow || prof || !grouped || (split && (fork == 0 || fork == 2));
+    const bool forked = !serial && split;
+    const bool flow_first = !fuse_flow && serial && p.fuse_lookup && fork == 2 && !prof && grouped;
+    const bool lookup_alone = p.fuse_lookup || prof || !grouped || ondemand;       // (it cannot take convf1 into its launch)
+    p.flow = fuse_flow ? FLOW_FUSED : forked ? FLOW_SIDE : flow_first ? FLOW_FIRST : lookup_alone ? FLOW_AFTER_LOOKUP : FLOW_WITH_LOOKUP;
+    p.pair_second = !forked && grouped && r.arith == MFTX_ARITH_F32;
+    // both layers of the flow head on the tile-resident kernel (TC_RELU_PROJ) + a stencil sum ...
+    p.head_fused = tile_w(W_FH1) && r.wproj != nullptr && opt[MFTX_RAFT_OPT_FUSE_HEAD] != 0;
+    // ... and, with the flow branch fused too, an iteration's update is left pending for the next iteration's flow-branch kernel
+    // (which reads every cell of its tile anyway); the last one, and every one under a debug trace, by a launch of its own
+    p.defer_update = p.head_fused && fuse_flow && opt[MFTX_RAFT_OPT_FUSE_HEAD] != 2 && !trace;
+    p.ou_fused = p.tiles_on && r.wou != nullptr && opt[MFTX_RAFT_OPT_FUSE_OU] != 0;
+    p.ou_materialised = !p.ou_fused || opt[MFTX_RAFT_OPT_FUSE_OU] == 2;      // (2: the fused kernel on the materialised input -- A/B, tests)
+    // Everything between the first kernels (which read the caller's feature maps) and the last (which writes the caller's outputs) touches the
+    // workspace only: one launch sequence per (shape, workspace, mode), replayed as a hipGraph from its third use on (graph_cache.h)
+    p.use_graph = r.graphs && opt[MFTX_RAFT_OPT_GRAPH] != 0 && !prof && !trace && !ondemand;
+    p.side_stream = split && fork != 0;      // created ahead of a capture, never inside one (a superset of flow == FLOW_SIDE)
+    return p;
+}
+
+extern "C" int mftx_raft_plan(const mftx_raft *r, int P, int h, int w, int ctx_supplied, int *out, int n) {
+    if (!r || r->magic != RAFT_MAGIC) return fail(MFTX_E_STATE, "raft_plan: bad handle");
+    if (P <= 0 || h <= 0 || w <= 0) return fail(MFTX_E_ARG, "raft_plan: need P, h, w >= 1");
+    if (!out || n != MFTX_RAFT_PLAN_FIELDS) return fail(MFTX_E_ARG, "raft_plan: need %d slots", MFTX_RAFT_PLAN_FIELDS);
+    const RefinePlan p = refine_plan(*r, P, h, w, ctx_supplied != 0, prof_enabled(), r->coords_trace != nullptr);
+    const int v[MFTX_RAFT_PLAN_FIELDS] = {p.SP, p.fuse_lookup, p.tiles_on, p.gru_fused, p.ctx_supplied, p.two_pass, (int)p.flow, p.pair_second,
+                                          p.head_fused, p.defer_update, p.ou_fused, p.ou_materialised, p.use_graph, p.side_stream};
+    for (int i = 0; i < n; ++i) out[i] = v[i];
+    return 0;
 }
 
 // gather (optional): the pairs' maps through per-pair pointers (fmap1 / fmap2 / net / inp are then unused); f2_shared: every
@@ -413,41 +466,273 @@ static mftx_conv_desc conv_desc(const float *a0, int lda0, int c0, const float *
 // CtxTable), f1s the split form of the first maps, f2s the split form of the shared second map
 struct RefineGather { PairPtrs f1, f2, net, inp; bool f2_shared; bool has_ctx, has_f1s; PairPtrs ctx[4], f1s; const float *f2s; };
 
-// The context features' third of the four GRU gate sums (+ bias): zr[pass] [M][256], q[pass] [M][128] from `inp` ([M][128] at stride
-// ld; split form when sp).  ONE place for the refinement and for mftx_raft_frame_prepare: the same kernels, the same bits.
-static int launch_context_parts(const mftx_raft *r, bool tiles_on, bool sp, const float *inp, int ld, int P, int h, int w,
-                                float *const zr[2], float *const q[2], hipStream_t s) {
-    const float *const *W = r->w;
-    const float *const *G = r->wg;
-    for (int pass = 0; pass < 2; ++pass) {
-        const int kh = pass ? 5 : 1, kw = pass ? 1 : 5;
-        const int slot[2] = {pass ? W_ZR2_INP : W_ZR1_INP, pass ? W_Q2_INP : W_Q1_INP};
-        const float *bias[2] = {W[pass ? B_ZR2 : B_ZR1], W[pass ? B_Q2 : B_Q1]};
-        float *out[2] = {zr[pass], q[pass]};
-        for (int k = 0; k < 2; ++k) {
-            const int N = k ? 128 : 256;
-            if (tiles_on && r->wt[slot[k]]) {
-                TileConvLaunch t{};
-                t.a0 = inp; t.lda0 = ld; t.cin = 128; t.wf = r->wt[slot[k]]; t.bias = bias[k];
-                t.P = P; t.h = h; t.w = w; t.N = N; t.kh = kh; t.kw = kw; t.epi = 0;
-                t.cells = r->opt[MFTX_RAFT_OPT_TILE_CELLS];
-                t.out = out[k]; t.ldo = N;
-                TRY(launch_tile_conv(t, s));
-            } else {
-                mftx_conv_desc d = conv_desc(inp, ld, 128, nullptr, 0, 0, G[slot[k]], bias[k], out[k], N, P, h, w, N, kh, kw, 0);
-                d.arith = r->arith; d.a_split = sp; d.out_split = false;
-                TRY(launch_conv(d, s));
+// The coordinates the iteration works on.  With a deferred update (RefinePlan) the next iteration's flow-branch kernel applies it
+// into the other of two buffers -- flo1 is free then; only the last update is applied by flow_head_sum_kernel, into coords1.
+struct Coords { float *cur, *alt; bool pending; };     // pending: ws.fh holds an update (T) that cur does not contain yet
+struct Seg { const float *p; int ld, c; };             // an input segment: c channels per cell, cell m at p + m * ld
+struct Out { float *p; int ld, N; };                   // N output channels per cell, cell m at p + m * ld
+enum { ACT_NONE, ACT_RELU, ACT_GRU_ZR, ACT_GRU_Q };    // mftx_conv_desc.act = the tile-resident kernel's epilogue
+
+// one call: what its stages work on (filled in one place each: refine_impl, mftx_raft_frame_prepare), and the stages
+struct RefineCall {
+    mftx_raft *r;
+    const float *const *W, *const *G;  // r->w; r->wg (GEMM layers: fp32 or split weights, by the handle's arithmetic)
+    RefinePlan plan;
+    hipStream_t s;
+    int P, h, w, iters;
+    Workspace ws;
+    const float *lv[4];                // the stored pyramid (ws.lvl)
+    const float *fmap1, *f2lv[4];      // on-demand correlation: the query features, the second map and its pooled levels
+    float *flow_lr;
+
+    // a stride-1, same-padded layer over the batch in fp32 arithmetic ...
+    mftx_conv_desc conv_desc(Seg a0, Seg a1, const float *wpk, const float *bias, Out out, int kh, int kw, int act) const {
+        mftx_conv_desc d{};
+        d.a0 = a0.p; d.lda0 = a0.ld; d.c0 = a0.c; d.a1 = a1.p; d.lda1 = a1.ld; d.c1 = a1.c;
+        d.wpk = wpk; d.bias = bias; d.out = out.p; d.ldo = out.ld; d.N = out.N; d.P = P; d.h = h; d.w = w;
+        d.kh = kh; d.kw = kw; d.act = act; d.out_scale = 1.f;
+        return d;
+    }
+    // ... and in the handle's; a: the A operand(s) are in split form, o: the output is written in it (where the plan keeps activations so)
+    mftx_conv_desc gemm(mftx_conv_desc d, bool a = true, bool o = false) const {
+        d.arith = r->arith; d.a_split = plan.SP && a; d.out_split = plan.SP && o; return d;
+    }
+    TileConvLaunch tile_launch(int slot, const float *bias, Seg a0, Seg a1, int N, int kh, int kw, int epi) const {
+        TileConvLaunch t{};
+        t.a0 = a0.p; t.lda0 = a0.ld; t.a1 = a1.p; t.lda1 = a1.ld; t.cin = a1.p ? 256 : 128; t.wf = r->wt[slot]; t.bias = bias;
+        t.P = P; t.h = h; t.w = w; t.N = N; t.kh = kh; t.kw = kw; t.epi = epi;
+        t.cells = r->opt[MFTX_RAFT_OPT_TILE_CELLS];
+        return t;
+    }
+    // A layer that exists in both kernel families, input segments of 128 split-form channels: the tile-resident kernel where the plan
+    // runs it and the slot's weight stream is set, else the ring-buffered GEMM.  out_split: the output in split form (where the plan
+    // keeps activations so); g, addend (act = ACT_GRU_*): the gate epilogue's operands, the context part added in front of it
+    int conv_layer(int slot, const float *bias, Seg a0, Seg a1, Out out, int kh, int kw, int act, bool out_split, const GruEpilogue *g = nullptr,
+                   const float *addend = nullptr, int ld_addend = 0) const {
+        if (plan.tiles_on && r->wt[slot]) {
+            TileConvLaunch t = tile_launch(slot, bias, a0, a1, out.N, kh, kw, act);
+            t.addend = addend; t.ld_addend = ld_addend;
+            if (!g) { t.out = out.p; t.ldo = out.ld; t.out_split = out_split ? 1 : 0; }
+            else {        // (each epilogue is handed what it reads and writes, no more)
+                t.z = g->z; t.hf = g->hf; t.ld_hf = g->ld_hf;
+                if (act == ACT_GRU_ZR) t.rh = g->rh; else { t.hx = g->hx; t.ld_hx = g->ld_hx; }
+            }
+            return launch_tile_conv(t, s);
+        }
+        mftx_conv_desc d = gemm(conv_desc(a0, a1, G[slot], bias, out, kh, kw, act), true, out_split);
+        d.addend = addend; d.ld_addend = ld_addend;
+        return g ? launch_conv_gru(d, *g, s) : launch_conv(d, s);
+    }
+    // The context features' third of the four GRU gate sums (+ bias): zr[pass] [M][256], q[pass] [M][128] from `inp` ([M][128] at stride
+    // ld; split form where the plan keeps activations so).  ONE place for the refinement and for mftx_raft_frame_prepare: the same kernels,
+    // the same bits.  Reads r, plan.tiles_on, plan.SP, the shape and the stream, nothing else.
+    int context_parts(const float *inp, int ld, float *const zr[2], float *const q[2]) const {
+        for (int pass = 0; pass < 2; ++pass) {
+            const int kh = pass ? 5 : 1, kw = pass ? 1 : 5;
+            TRY(conv_layer(pass ? W_ZR2_INP : W_ZR1_INP, W[pass ? B_ZR2 : B_ZR1], Seg{inp, ld, 128}, Seg{}, Out{zr[pass], 256, 256}, kh, kw, ACT_NONE, false));
+            TRY(conv_layer(pass ? W_Q2_INP : W_Q1_INP, W[pass ? B_Q2 : B_Q1], Seg{inp, ld, 128}, Seg{}, Out{q[pass], 128, 128}, kh, kw, ACT_NONE, false));
+        }
+        return 0;
+    }
+    // correlation volume + pyramid (core/corr.py:14-28)
+    int volume(const float *fmap2, const RefineGather *gather) const {
+        if (r->ondemand) return launch_fmap_pyramid(fmap2, P, 256, h, w, ws.f2l, s);   // core/corr.py:78-82 (only fmap2's pyramid is used)
+        if (!gather) return launch_corr_pyramid(fmap1, fmap2, P, 256, h, w, ws.lvl, s, r->arith == MFTX_ARITH_SPLIT ? ws.f2s : nullptr, r->opt[MFTX_RAFT_OPT_TILE_VOLUME]);
+        // gathered pairs (split arithmetic, tile-resident volume: checked by the caller): the second maps are split into the
+        // workspace -- once when all pairs share one -- and the volume kernel takes every pair's first map where it lies
+        // (a frame prepared ahead brings its split map along: nothing to split for the second map, nothing to split in the volume
+        // kernel's K loop for the first)
+        const long long pair_floats = (long long)h * w * 256;
+        const float *f2s = ws.f2s;
+        if (gather->f2_shared && gather->f2s) f2s = gather->f2s;
+        else if (gather->f2_shared) TRY(launch_split_weights(gather->f2.p[0], ws.f2s, pair_floats, s));
+        else for (int b = 0; b < P; ++b) TRY(launch_split_weights(gather->f2.p[b], ws.f2s + b * pair_floats, pair_floats, s));
+        return launch_volume_tile(nullptr, f2s, P, h, w, ws.lvl, s, gather->has_f1s ? &gather->f1s : &gather->f1, gather->f2_shared ? 0 : pair_floats,
+                                  gather->has_f1s);
+    }
+    int init_state(const float *net, const float *inp, const float *flow_init, const RefineGather *gather) const {
+        const int M = P * h * w;
+        const long long slots = (long long)M * 64;
+        ProfScope prof(PC_GLUE, s, 0);
+        InitGather ga{};
+        if (gather) { ga.on = 1; ga.netp = gather->net; ga.inpp = gather->inp; }
+        CtxTable ct{};
+        if (plan.gru_fused) {
+            ct.table = ws.ctx;
+            ct.own[0] = ws.pre_zr[0]; ct.own[1] = ws.pre_q[0]; ct.own[2] = ws.pre_zr[1]; ct.own[3] = ws.pre_q[1];
+            ct.supplied = plan.ctx_supplied ? 1 : 0;
+            if (plan.ctx_supplied) for (int k = 0; k < 4; ++k) ct.parts[k] = gather->ctx[k];
+        }
+        hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, net, inp,
+                           flow_init, ws.hx, plan.SP ? ws.hf : nullptr, ws.coords1, M, h, w, ga, ct);
+        return check_launch("init_state");
+    }
+    // convc2 / conv: 3 x 3 over 256 split-form channels, relu, split-form output; pair: another relu layer to go out in the same launch
+    int conv256(int slot, const float *bias, const float *in, Out out, const mftx_conv_desc *pair = nullptr) const {
+        if (plan.two_pass) return launch_tile_conv2p(in, 256, r->wt[slot], bias, out.p, out.ld, out.N, P, h, w, r->opt[MFTX_RAFT_OPT_TILE_CELLS], s);
+        const mftx_conv_desc d = gemm(conv_desc(Seg{in, 256, 256}, Seg{}, G[slot], bias, out, 3, 3, ACT_RELU), true, true);
+        return pair ? launch_conv_pair(d, *pair, s) : launch_conv(d, s);
+    }
+    // The correlation branch: lookup -> convc1 -> ws.cor1 -> convc2 -> corflo[0 .. 192).  f1: convf1 goes with the lookup
+    // (FLOW_WITH_LOOKUP: in its launch, FLOW_AFTER_LOOKUP: behind it); pair: convf2, to go out with convc2 (plan.pair_second).
+    // With the fused kernel the features themselves are needed once, by the OU heads behind the last iteration.
+    int corr_branch(const float *coords, bool last, const ConvF1Args *f1 = nullptr, int f1_blocks = 0, const mftx_conv_desc *pair = nullptr) const {
+        if (plan.flow == FLOW_WITH_LOOKUP) {        // (never with the fused or the on-demand lookup: refine_plan)
+            const LookupArgs la = make_lookup_args(lv, coords, P, h, w, ws.corr, ws.ld_corr);
+            const int lookup_blocks = cdiv(cdiv(la.cells, 2), LK_WAVES);
+            hipLaunchKernelGGL(lookup_convf1_kernel, dim3(lookup_blocks + f1_blocks), dim3(256), 0, s, la, *f1, lookup_blocks, f1_blocks);
+        } else {
+            if (plan.fuse_lookup) {
+                if (last && plan.flow != FLOW_SIDE) TRY(launch_corr_lookup(lv, coords, P, h, w, ws.corr, ws.ld_corr, s));      // (FLOW_SIDE: off the critical path)
+                TRY(launch_lookup_convc1(lv, coords, P, h, w, r->wfused, W[B_CONVC1], ws.cor1, 256, 1, s));
+            } else if (r->ondemand) TRY(launch_corr_ondemand(fmap1, f2lv, coords, P, h, w, ws.corr, ws.ld_corr, s));
+            else TRY(launch_corr_lookup(lv, coords, P, h, w, ws.corr, ws.ld_corr, s));
+            if (f1) {
+                ProfScope prof(PC_CONVF1, s, 2.0 * P * h * w * 128 * 98);
+                hipLaunchKernelGGL(convf1_kernel, dim3(f1_blocks), dim3(256), 0, s, *f1);
             }
         }
+        TRY(check_launch("lookup + convf1"));
+        if (!plan.fuse_lookup)
+            TRY(launch_conv(gemm(conv_desc(Seg{ws.corr, ws.ld_corr, ws.ld_corr}, Seg{}, G[W_CONVC1], W[B_CONVC1], Out{ws.cor1, 256, 256}, 1, 1, ACT_RELU), false, true), s));
+        return conv256(W_CONVC2, W[B_CONVC2], ws.cor1, Out{ws.corflo, 256, 192}, pair);
     }
-    return 0;
-}
-static int refine_impl(mftx_raft *r, int P, int h, int w, int iters, const float *fmap1,
-                                const float *fmap2, const float *net, const float *inp, const float *flow_init,
-                                int pad_left,
-                                int pad_right, int pad_top, int pad_bottom, float *flow, float *occl,
-                                float *sigma, float *packed, float *flow_lr_out, void *workspace,
-                                size_t workspace_bytes, void *stream, const RefineGather *gather) {
+    // motion encoder (core/update.py:152-160): -> the motion features in hx[256 .. 384)
+    int motion_encoder(Coords &x, bool last) const {
+        const int strips = cdiv(w, F1_CELLS);
+        const ConvF1Args f1{x.cur, W[W_CONVF1], W[B_CONVF1], ws.flo1, ws.hx, h, w, strips, P * h * strips, plan.SP ? 1 : 0};
+        const int f1_blocks = cdiv(f1.n_strips, 2);
+        const Out flo{ws.corflo + 192, 256, 64};         // the flow branch's part of conv's input
+        const mftx_conv_desc f2 = gemm(conv_desc(Seg{ws.flo1, 128, 128}, Seg{}, G[W_CONVF2], W[B_CONVF2], flo, 3, 3, ACT_RELU), true, true);
+        switch (plan.flow) {
+        case FLOW_FUSED:
+            if (x.pending) {       // ... which also applies the pending update, into the other buffer
+                TRY(launch_flow_branch(x.cur, P, h, w, r->wflow, W[B_CONVF1], W[B_CONVF2], flo.p, flo.ld, ws.hx, 384, s, ws.fh, W[B_FH2], x.alt, ws.delta));
+                x = Coords{x.alt, x.cur, false};
+            } else TRY(launch_flow_branch(x.cur, P, h, w, r->wflow, W[B_CONVF1], W[B_CONVF2], flo.p, flo.ld, ws.hx, 384, s));
+            TRY(corr_branch(x.cur, last));
+            break;
+        case FLOW_SIDE:
+            TRY(ensure_side_stream(r));
+            if (hipEventRecord(r->ev_fork, s) != hipSuccess || hipStreamWaitEvent(r->side, r->ev_fork, 0) != hipSuccess)
+                return fail(MFTX_E_STATE, "raft_refine: fork onto the side stream failed");
+            hipLaunchKernelGGL(convf1_kernel, dim3(f1_blocks), dim3(256), 0, r->side, f1);
+            TRY(check_launch("convf1"));
+            TRY(launch_conv(f2, r->side));
+            if (plan.fuse_lookup && last) TRY(launch_corr_lookup(lv, x.cur, P, h, w, ws.corr, ws.ld_corr, r->side));
+            if (hipEventRecord(r->ev_join, r->side) != hipSuccess) return fail(MFTX_E_STATE, "raft_refine: join event failed");
+            TRY(corr_branch(x.cur, last));
+            if (hipStreamWaitEvent(s, r->ev_join, 0) != hipSuccess) return fail(MFTX_E_STATE, "raft_refine: join failed");
+            break;
+        case FLOW_FIRST:
+            hipLaunchKernelGGL(convf1_kernel, dim3(f1_blocks), dim3(256), 0, s, f1);
+            TRY(check_launch("convf1"));
+            TRY(launch_conv(f2, s));
+            TRY(corr_branch(x.cur, last));
+            break;
+        case FLOW_AFTER_LOOKUP: case FLOW_WITH_LOOKUP:
+            TRY(corr_branch(x.cur, last, &f1, f1_blocks, plan.pair_second ? &f2 : nullptr));
+            if (!plan.pair_second) TRY(launch_conv(f2, s));
+            break;
+        }
+        return conv256(W_CONV, W[B_CONV], ws.corflo, Out{ws.hx + 256, 384, 126});
+    }
+    // SepConvGRU (core/update.py:108-123): horizontal 1x5 then vertical 5x1.  The gate convolutions are linear in their input
+    // [h | inp | motion] and `inp` does not change over the iterations (core/raft.py:146-149): its third of every gate sum (+ bias)
+    // is computed once (context_parts, or per frame: mftx_raft_frame_prepare) and enters here as an addend.  Same terms, summed once.
+    int gru() const {
+        for (int pass = 0; pass < 2; ++pass) {
+            const int kh = pass ? 5 : 1, kw = pass ? 1 : 5;
+            const int szr = pass ? W_ZR2_DYN : W_ZR1_DYN, sq = pass ? W_Q2_DYN : W_Q1_DYN;
+            if (plan.gru_fused) {
+                // the whole pass as ONE kernel (tile_conv.hip: gru_half_kernel): the tile is loaded once, r * h stays in LDS; h goes
+                // hx -> hb in the horizontal pass and back in the vertical one (a tile's halo cells are its neighbours' outputs)
+                GruHalfLaunch g{};
+                g.h_in = pass ? ws.hb : ws.hx; g.ld_hin = pass ? 128 : 384; g.h_out = pass ? ws.hx : ws.hb; g.ld_hout = pass ? 384 : 128;
+                g.mo = ws.hx + 256; g.ld_mo = 384; g.wzr = r->wt[szr]; g.wq = r->wt[sq]; g.pre_zr = ws.pre_zr[pass]; g.pre_q = ws.pre_q[pass]; g.ctx = ws.ctx;
+                g.z = ws.z; g.hf_in = pass ? ws.hfb : ws.hf; g.hf_out = pass ? ws.hf : ws.hfb; g.P = P; g.h = h; g.w = w; g.pass = pass; g.cells = r->opt[MFTX_RAFT_OPT_TILE_CELLS];
+                TRY(launch_gru_half(g, s));
+                continue;
+            }
+            const Seg motion{ws.hx + 256, 384, 128};
+            const GruEpilogue g1{1, ws.hx, 384, ws.z, ws.rh, plan.SP ? ws.hf : nullptr, 128}, g2{2, ws.hx, 384, ws.z, ws.rh, plan.SP ? ws.hf : nullptr, 128};
+            TRY(conv_layer(szr, nullptr, Seg{ws.hx, 384, 128}, motion, Out{ws.z, 128, 256}, kh, kw, ACT_GRU_ZR, true, &g1, ws.pre_zr[pass], 256));
+            TRY(conv_layer(sq, nullptr, Seg{ws.rh, 128, 128}, motion, Out{ws.hx, 384, 128}, kh, kw, ACT_GRU_Q, true, &g2, ws.pre_q[pass], 128));
+        }
+        return 0;
+    }
+    // flow head (core/update.py:6-14) and coordinate update (core/raft.py:184)
+    int flow_head(Coords &x, bool last) const {
+        const Seg hidden{ws.hx, 384, 128};
+        if (plan.head_fused) {
+            // both layers: relu(conv1) stays in LDS, multiplied there with conv2's filter as [256 x 18] partial products per cell
+            // (-> ws.fh, [M][18]); the nine shifted terms are added, and the coordinates updated, by a small kernel
+            TileConvLaunch t = tile_launch(W_FH1, W[B_FH1], hidden, Seg{}, 256, 3, 3, 4);
+            t.wproj = r->wproj; t.tout = ws.fh;
+            TRY(launch_tile_conv(t, s));
+            if (!last && plan.defer_update) { x.pending = true; return 0; }
+            float *dst = last ? ws.coords1 : x.cur;      // (the last one into coords1, whichever buffer is current)
+            TRY(launch_flow_head_sum(ws.fh, W[B_FH2], ws.delta, x.cur, dst, P, h, w, s));
+            x.cur = dst;
+            return 0;
+        }
+        TRY(conv_layer(W_FH1, W[B_FH1], hidden, Seg{}, Out{ws.fh, 256, 256}, 3, 3, ACT_RELU, false));
+        // last layer of the flow head, fused with coords1 += delta_flow (core/raft.py:184)
+        const mftx_conv_desc fh2 = conv_desc(Seg{ws.fh, 256, 256}, Seg{}, W[W_FH2], W[B_FH2], Out{ws.delta, 2, 2}, 3, 3, ACT_NONE);
+        if (!conv_small_applicable(fh2)) return fail(MFTX_E_STATE, "raft_refine: flow-head layer does not fit the small-N kernel");
+        return launch_conv_small(fh2, s, x.cur, 2);
+    }
+    // What is consumed only after the last iteration in test mode: the upsampling mask (core/raft.py:190-196,234-239) and the
+    // occlusion + uncertainty heads (core/update.py:196-214)
+    int final_heads(const float *coords) const {
+        const int M = P * h * w;
+        // (the hidden 256 channels go to the 1 x 1 layer in split form: a GEMM that splits its A operand in registers runs at half the
+        // matrix utilisation of one that finds it split -- profiles/r4k_pmc_mfma_util.csv: 0.18 against 0.35)
+        TRY(conv_layer(W_MASK0, W[B_MASK0], Seg{ws.hx, 384, 128}, Seg{}, Out{ws.fh, 256, 256}, 3, 3, ACT_RELU, true));
+        mftx_conv_desc mask2 = gemm(conv_desc(Seg{ws.fh, 256, 256}, Seg{}, G[W_MASK2], W[B_MASK2], Out{ws.mask, 576, 576}, 1, 1, ACT_NONE));
+        mask2.out_scale = 0.25f;
+        TRY(launch_conv(mask2, s));
+        if (plan.ou_materialised) {
+            const long long slots = (long long)M * 178;
+            ProfScope prof(PC_GLUE, s, 0);
+            hipLaunchKernelGGL(ou_gather_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, ws.hx,
+                               ws.corr, ws.ld_corr, coords, ws.delta, ws.ouin, flow_lr, M, h, w, plan.SP ? 1 : 0);
+            TRY(check_launch("ou_gather"));
+        }
+        if (plan.ou_fused) {
+            // both layers of both heads as ONE tile-resident kernel (five channel passes over the 712-channel input, the 3 x 3 x 3 second
+            // layers as a projection epilogue; T -> ws.ouh) + a stencil sum; the input is gathered from its parts by the kernel's loader
+            const OuGather ga{ws.hx, ws.corr, ws.ld_corr, coords, ws.delta, flow_lr};
+            return launch_ou_heads(plan.ou_materialised ? ws.ouin : nullptr, 712, P, h, w, r->wou, W[B_OU1], r->wouproj, W[B_OU2], ws.ouh, ws.ou, 4, r->opt[MFTX_RAFT_OPT_TILE_CELLS], s,
+                                   plan.ou_materialised ? nullptr : &ga);
+        }
+        TRY(launch_conv(gemm(conv_desc(Seg{ws.ouin, 712, 712}, Seg{}, G[W_OU1], W[B_OU1], Out{ws.ouh, 256, 256}, 3, 3, ACT_RELU)), s));
+        return launch_conv(conv_desc(Seg{ws.ouh, 256, 256}, Seg{}, W[W_OU2], W[B_OU2], Out{ws.ou, 4, 3}, 3, 3, ACT_NONE), s);
+    }
+    // Everything between init_state and the convex upsampling: touches the workspace only (captured as one graph: RefinePlan.use_graph;
+    // the forked side stream joins the capture through its events)
+    int core() const {
+        const size_t n = (size_t)P * h * w * 2;        // floats of one coordinate map
+        float *trace = r->coords_trace;                // RAFT.forward(vis_debug=True): the coordinates every iteration starts from (core/raft.py:175-176) ...
+        if (!plan.ctx_supplied) TRY(context_parts(ws.hx + 128, 384, ws.pre_zr, ws.pre_q));
+        Coords x{ws.coords1, ws.flo1, false};
+        for (int it = 0; it < iters; ++it) {
+            const bool last = (it == iters - 1);
+            if (trace && hipMemcpyAsync(trace + it * n, x.cur, n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+                return fail(MFTX_E_STATE, "raft_refine: coords trace copy failed");
+            TRY(motion_encoder(x, last));
+            TRY(gru());
+            TRY(flow_head(x, last));
+        }
+        if (trace && hipMemcpyAsync(trace + iters * n, x.cur, n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)       // ... and the final ones (core/raft.py:255-256)
+            return fail(MFTX_E_STATE, "raft_refine: coords trace copy failed");
+        return final_heads(x.cur);
+    }
+};
+
+static int refine_impl(mftx_raft *r, int P, int h, int w, int iters, const float *fmap1, const float *fmap2, const float *net,
+                       const float *inp, const float *flow_init, int pad_left, int pad_right, int pad_top, int pad_bottom, float *flow, float *occl,
+                       float *sigma, float *packed, float *flow_lr_out, void *workspace, size_t workspace_bytes, void *stream, const RefineGather *gather) {
     if (!r || r->magic != RAFT_MAGIC) return fail(MFTX_E_STATE, "raft_refine: bad handle");
     const bool planar = flow && occl && sigma;
     if (gather) { fmap1 = gather->f1.p[0]; fmap2 = gather->f2.p[0]; net = gather->net.p[0]; inp = gather->inp.p[0]; }      // (for the checks below)
@@ -456,313 +741,36 @@ static int refine_impl(mftx_raft *r, int P, int h, int w, int iters, const float
     if (P <= 0 || h < 16 || w < 16 || iters < 1)
         return fail(MFTX_E_ARG, "raft_refine: need P >= 1, h, w >= 16 (level 3 of the pyramid needs >= 2 cells), iters >= 1");
     if ((long long)P * h * w > (1ll << 24)) return fail(MFTX_E_ARG, "raft_refine: batch too large");
-    if (!aligned16(fmap1) || !aligned16(fmap2) || !aligned16(net) || !aligned16(inp) ||
-        (reinterpret_cast<uintptr_t>(workspace) & 255))
+    if (!aligned16(fmap1) || !aligned16(fmap2) || !aligned16(net) || !aligned16(inp) || (reinterpret_cast<uintptr_t>(workspace) & 255))
         return fail(MFTX_E_ALIGN, "raft_refine: inputs must be 16-byte and the workspace 256-byte aligned");
-    if (pad_left < 0 || pad_right < 0 || pad_top < 0 || pad_bottom < 0 || pad_left + pad_right >= 8 ||
-        pad_top + pad_bottom >= 8)
+    if (pad_left < 0 || pad_right < 0 || pad_top < 0 || pad_bottom < 0 || pad_left + pad_right >= 8 || pad_top + pad_bottom >= 8)
         return fail(MFTX_E_ARG, "raft_refine: bad padding");
-    const bool ondemand = r->ondemand != 0;
-    // split arithmetic: every tensor that feeds a GEMM of the update block / OU heads lives in the workspace in SPLIT
-    // form (common.h), written that way by its producer -- the GEMMs' K loops then spend nothing on splitting
-    const bool SP = r->arith == MFTX_ARITH_SPLIT && r->opt[MFTX_RAFT_OPT_PRESPLIT] != 0;
-    // lookup fused into convc1 (csrc/lookup_convc1.hip): the 324 features stay in LDS; they are materialised on the last
-    // iteration only, for the occlusion / uncertainty heads
-    const bool fuse_lookup = SP && !ondemand && r->wfused != nullptr && r->opt[MFTX_RAFT_OPT_FUSE_LOOKUP] != 0 &&
-                             lookup_convc1_applicable(P, h, w, 256);
-    Workspace ws = carve(workspace, P, h, w, ondemand, r->arith == MFTX_ARITH_SPLIT);
+    const RefinePlan plan = refine_plan(*r, P, h, w, gather && gather->has_ctx, prof_enabled(), r->coords_trace != nullptr);
+    const Workspace ws = carve(workspace, P, h, w, r->ondemand != 0, r->arith == MFTX_ARITH_SPLIT);
     if (ws.bytes > workspace_bytes)
         return fail(MFTX_E_WORKSPACE, "raft_refine: workspace %zu < %zu bytes", workspace_bytes, ws.bytes);
-    hipStream_t s = (hipStream_t)stream;
-    const bool use_graph = r->graphs && r->opt[MFTX_RAFT_OPT_GRAPH] != 0 && !prof_enabled() && !r->coords_trace && !ondemand;
-    hipStream_t caller = s;
+    hipStream_t s = (hipStream_t)stream, caller = s;
     bool proxied = false;
-    if (use_graph && s == nullptr) {                 // the legacy stream (PyTorch's default) cannot be captured: graph_cache.h
+    if (plan.use_graph && s == nullptr) {            // the legacy stream (PyTorch's default) cannot be captured: graph_cache.h
         hipStream_t own = r->graphs->proxy.enter(s);
         if (own) { s = own; proxied = true; }
     }
     struct Leave { GraphCache *g; hipStream_t caller; bool on; ~Leave() { if (on) g->proxy.leave(caller); } } leave{r->graphs, caller, proxied};
-    const int N = h * w, M = P * N;
-    const float *const *W = r->w;
-    const float *const *G = r->wg;          // GEMM layers: fp32 or split weights, by the handle's arithmetic
-    const int AR = r->arith;
-    // gemm(desc, a, o): arithmetic of the handle; a: the A operand(s) are in split form, o: the output is written in it
-    auto gemm = [AR, SP](mftx_conv_desc d, bool a = true, bool o = false) { d.arith = AR; d.a_split = SP && a; d.out_split = SP && o; return d; };
-
-    // correlation volume + pyramid (core/corr.py:14-28)
-    const float *f2lv[4] = {fmap2, ws.f2l[0], ws.f2l[1], ws.f2l[2]};
-    if (ondemand) TRY(launch_fmap_pyramid(fmap2, P, 256, h, w, ws.f2l, s));   // core/corr.py:78-82 (only fmap2's pyramid is used)
-    else if (gather) {
-        // gathered pairs (split arithmetic, tile-resident volume: checked by the caller): the second maps are split into the
-        // workspace -- once when all pairs share one -- and the volume kernel takes every pair's first map where it lies
-        const long long pair_floats = (long long)N * 256;
-        // (a frame prepared ahead brings its split map along: nothing to split for the second map, nothing to split in the volume
-        // kernel's K loop for the first)
-        const float *f2s = ws.f2s;
-        if (gather->f2_shared && gather->f2s) f2s = gather->f2s;
-        else if (gather->f2_shared) TRY(launch_split_weights(gather->f2.p[0], ws.f2s, pair_floats, s));
-        else for (int b = 0; b < P; ++b) TRY(launch_split_weights(gather->f2.p[b], ws.f2s + b * pair_floats, pair_floats, s));
-        TRY(launch_volume_tile(nullptr, f2s, P, h, w, ws.lvl, s, gather->has_f1s ? &gather->f1s : &gather->f1, gather->f2_shared ? 0 : pair_floats,
-                               gather->has_f1s));
-    }
-    else TRY(launch_corr_pyramid(fmap1, fmap2, P, 256, h, w, ws.lvl, s, r->arith == MFTX_ARITH_SPLIT ? ws.f2s : nullptr, r->opt[MFTX_RAFT_OPT_TILE_VOLUME]));
-    // Layers whose input tile fits a CU's LDS run on the tile-resident kernel (csrc/tile_conv.hip) when its weight streams are set
-    // (option value 2: whatever the batch; 1, the default: only when the tiles fill the chip -- at 256 x 256 pixels or one pair
-    // per GPU the ring-buffered kernel's small tiles win)
-    const bool tiles_on = SP && r->opt[MFTX_RAFT_OPT_TILE_CONV] != 0 &&
-                          (r->opt[MFTX_RAFT_OPT_TILE_CONV] == 2 ||
-                           (tile_conv_fills_chip(P, h, w, 3, 3) && tile_conv_fills_chip(P, h, w, 1, 5) && tile_conv_fills_chip(P, h, w, 5, 1)));
-    auto tile_w = [&](int slot) -> const void * { return tiles_on ? r->wt[slot] : nullptr; };
-    // SepConvGRU as one kernel per pass
-    // (decided ONCE for both passes: they hand h over through the ping-pong pair hx/hf <-> hb/hfb, so one fused and one
-    // unfused pass would read a buffer the other never wrote -- a partial set of tile weights runs both passes unfused)
-    const bool gru_fused = tile_w(W_ZR1_DYN) && tile_w(W_Q1_DYN) && tile_w(W_ZR2_DYN) && tile_w(W_Q2_DYN) &&
-                           r->opt[MFTX_RAFT_OPT_FUSE_GRU] != 0;
-    // context parts that came with the pairs are honoured where the fused pass reads them through the table; elsewhere they are
-    // computed here as ever
-    const bool ctx_supplied = gather && gather->has_ctx && gru_fused;
-    {
-        const long long slots = (long long)M * 64;
-        ProfScope prof(PC_GLUE, s, 0);
-        InitGather ga{};
-        if (gather) { ga.on = 1; ga.netp = gather->net; ga.inpp = gather->inp; }
-        CtxTable ct{};
-        if (gru_fused) {
-            ct.table = ws.ctx;
-            ct.own[0] = ws.pre_zr[0]; ct.own[1] = ws.pre_q[0]; ct.own[2] = ws.pre_zr[1]; ct.own[3] = ws.pre_q[1];
-            ct.supplied = ctx_supplied ? 1 : 0;
-            if (ctx_supplied) for (int k = 0; k < 4; ++k) ct.parts[k] = gather->ctx[k];
-        }
-        hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, net, inp,
-                           flow_init, ws.hx, SP ? ws.hf : nullptr, ws.coords1, M, h, w, ga, ct);
-        TRY(check_launch("init_state"));
-    }
-    float *flow_lr = flow_lr_out ? flow_lr_out : ws.flow_lr;
-    // Everything between the first kernels (which read the caller's feature maps) and the last (which writes the caller's
-    // outputs) touches the workspace only: one launch sequence per (shape, workspace, mode), replayed as a hipGraph from
-    // its third use on (graph_cache.h).  The forked side stream joins the capture through its events.
-    auto core = [&]() -> int {
-    // The gate convolutions are linear in their input [h | inp | motion] and `inp` does not change
-    // over the iterations (core/raft.py:146-149): its third of every gate sum (+ bias) is computed
-    // once here and enters the per-iteration GEMMs as an epilogue addend.  Same terms, summed once.
-    // (a frame's parts computed when it was encoded -- mftx_raft_frame_prepare -- arrive through the table instead)
-    auto tile_layer = [&](const float *a0, int lda0, const float *a1, int lda1, const void *wf, const float *bias, int N, int kh, int kw, int epi) {
-        TileConvLaunch t{};
-        t.a0 = a0; t.lda0 = lda0; t.a1 = a1; t.lda1 = lda1; t.cin = a1 ? 256 : 128; t.wf = wf; t.bias = bias;
-        t.P = P; t.h = h; t.w = w; t.N = N; t.kh = kh; t.kw = kw; t.epi = epi;
-        t.cells = r->opt[MFTX_RAFT_OPT_TILE_CELLS];
-        return t;
-    };
-    if (!ctx_supplied) TRY(launch_context_parts(r, tiles_on, SP, ws.hx + 128, 384, P, h, w, ws.pre_zr, ws.pre_q, s));
-    const float *lv[4] = {ws.lvl[0], ws.lvl[1], ws.lvl[2], ws.lvl[3]};
-    const int strips = cdiv(w, F1_CELLS);
-    // The coordinates the iteration works on.  With the flow branch and the flow head both fused, an iteration's update is
-    // applied by the NEXT iteration's flow-branch kernel (which reads every cell of its tile anyway) into the other of two
-    // buffers -- flo1 is free then -- instead of by a launch of its own; only the last update is applied by
-    // flow_head_sum_kernel, into coords1.
-    float *ccur = ws.coords1, *calt = ws.flo1;
-    bool pending = false;                    // ws.fh holds an update (T) that ccur does not contain yet
-    for (int it = 0; it < iters; ++it) {
-        const bool last = (it == iters - 1);
-        if (r->coords_trace &&       // RAFT.forward(vis_debug=True): the coordinates every iteration starts from (core/raft.py:175-176)
-            hipMemcpyAsync(r->coords_trace + (size_t)it * M * 2, ccur, (size_t)M * 8, hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return fail(MFTX_E_STATE, "raft_refine: coords trace copy failed");
-        // The motion encoder has two independent branches (core/update.py:152-158): correlation lookup -> convc1 -> convc2
-        // and convf1 -> convf2 on the flow.  Both need only coords1.  Split arithmetic, small batches (up to four
-        // 512 x 512 pairs: the kernels leave CUs idle): the flow branch runs on the handle's SIDE STREAM beside the
-        // correlation branch and joins in front of `conv` -- 3.67 -> 3.45 ms at one pair, 5.94 -> 5.59 at four
-        // (tools/bench_pairs.py).  At seven pairs this used to lose (every kernel filled the chip: 106.7 vs 111.5 frames/s);
-        // since convc2 runs as 224 workgroups of the 128 x 192 tile, 32 CUs are free beside it and its 1 x 1 predecessor
-        // for the flow branch's small kernels: 129.2 -> 130.3 frames/s (MFTX_RAFT_OPT_FORK = 0: in order on one stream, with
-        // lookup + convf1 as one launch).  fp32 MFMA keeps round 1's grouping (lookup + convf1 in one launch,
-        // convc2 + convf2 in one launch).  The per-kernel timing pass and MFTX_RAFT_OPT_GROUP = 0 run everything in order.
-        const ConvF1Args f1{ccur, W[W_CONVF1], W[B_CONVF1], ws.flo1, ws.hx, h, w, strips, P * h * strips, SP ? 1 : 0};
-        const int f1_blocks = cdiv(f1.n_strips, 2);
-        const bool nofuse = r->opt[MFTX_RAFT_OPT_GROUP] == 0, nopair = nofuse;
-        const mftx_conv_desc c2 = gemm(conv_desc(ws.cor1, 256, 256, nullptr, 0, 0, G[W_CONVC2], W[B_CONVC2], ws.corflo, 256, P, h, w, 192, 3, 3, 1), true, true);
-        const mftx_conv_desc f2 = gemm(conv_desc(ws.flo1, 128, 128, nullptr, 0, 0, G[W_CONVF2], W[B_CONVF2], ws.corflo + 192, 256, P, h, w, 64, 3, 3, 1), true, true);
-        const int fork_env = r->opt[MFTX_RAFT_OPT_FORK];      // 0 never, -1 / 1 with the split arithmetic
-        // the flow branch as ONE kernel (csrc/flow_branch.hip), in order on this stream: no side stream, no join
-        const bool fuse_flow = SP && r->wflow != nullptr && r->opt[MFTX_RAFT_OPT_FUSE_FLOW] != 0 && !nofuse;
-        if (fuse_flow) {
-            if (pending) {
-                TRY(launch_flow_branch(ccur, P, h, w, r->wflow, W[B_CONVF1], W[B_CONVF2], ws.corflo + 192, 256, ws.hx, 384, s, ws.fh, W[B_FH2], calt, ws.delta));
-                float *t = ccur; ccur = calt; calt = t;
-                pending = false;
-            } else TRY(launch_flow_branch(ccur, P, h, w, r->wflow, W[B_CONVF1], W[B_CONVF2], ws.corflo + 192, 256, ws.hx, 384, s));
-        }
-        const bool serial = fuse_flow || prof_enabled() || nofuse || (AR == MFTX_ARITH_SPLIT && (fork_env == 0 || fork_env == 2));
-        const bool forked = !serial && AR == MFTX_ARITH_SPLIT;
-        const bool flow_first = !fuse_flow && serial && fuse_lookup && fork_env == 2 && !prof_enabled() && !nofuse;    // convf1, convf2, then the correlation branch
-        if (flow_first) {
-            hipLaunchKernelGGL(convf1_kernel, dim3(f1_blocks), dim3(256), 0, s, f1);
-            TRY(check_launch("convf1"));
-            TRY(launch_conv(f2, s));
-        }
-        if (forked) {
-            TRY(ensure_side_stream(r));
-            if (hipEventRecord(r->ev_fork, s) != hipSuccess || hipStreamWaitEvent(r->side, r->ev_fork, 0) != hipSuccess)
-                return fail(MFTX_E_STATE, "raft_refine: fork onto the side stream failed");
-            hipLaunchKernelGGL(convf1_kernel, dim3(f1_blocks), dim3(256), 0, r->side, f1);
-            TRY(check_launch("convf1"));
-            TRY(launch_conv(f2, r->side));
-            // fused lookup: the features themselves are needed once, by ou_gather behind the last iteration -- off the critical path
-            if (fuse_lookup && last) TRY(launch_corr_lookup(lv, ccur, P, h, w, ws.corr, ws.ld_corr, r->side));
-            if (hipEventRecord(r->ev_join, r->side) != hipSuccess) return fail(MFTX_E_STATE, "raft_refine: join event failed");
-        }
-        // lookup + convf1 as ONE launch (HBM gathers beside VALU work) whenever the flow branch is not on the side stream:
-        // 113.7 vs 113.2 frames/s with the split arithmetic; the timing pass and MFTX_RAFT_OPT_GROUP = 0 keep them apart
-        if (fuse_lookup) {
-            if (last && !forked) TRY(launch_corr_lookup(lv, ccur, P, h, w, ws.corr, ws.ld_corr, s));
-            TRY(launch_lookup_convc1(lv, ccur, P, h, w, r->wfused, W[B_CONVC1], ws.cor1, 256, 1, s));
-            if (!forked && !flow_first && !fuse_flow) {
-                ProfScope prof(PC_CONVF1, s, 2.0 * M * 128 * 98);
-                hipLaunchKernelGGL(convf1_kernel, dim3(f1_blocks), dim3(256), 0, s, f1);
-            }
-        } else if (prof_enabled() || nofuse || forked || ondemand || fuse_flow) {
-            // (the 324 features stay fp32: written in split form the lookup takes 31 instead of 27 us, more than convc1
-            // gains from a pre-split A -- and its HBM roofline is the one with a north-star target)
-            if (ondemand) TRY(launch_corr_ondemand(fmap1, f2lv, ccur, P, h, w, ws.corr, ws.ld_corr, s));
-            else TRY(launch_corr_lookup(lv, ccur, P, h, w, ws.corr, ws.ld_corr, s));
-            if (!forked && !fuse_flow) {
-                ProfScope prof(PC_CONVF1, s, 2.0 * M * 128 * 98);
-                hipLaunchKernelGGL(convf1_kernel, dim3(f1_blocks), dim3(256), 0, s, f1);
-            }
-        } else {
-            const LookupArgs la = make_lookup_args(lv, ccur, P, h, w, ws.corr, ws.ld_corr);
-            const int lookup_blocks = cdiv(cdiv(la.cells, 2), LK_WAVES);
-            hipLaunchKernelGGL(lookup_convf1_kernel, dim3(lookup_blocks + f1_blocks), dim3(256), 0, s, la, f1,
-                               lookup_blocks, f1_blocks);
-        }
-        TRY(check_launch("lookup + convf1"));
-        // motion encoder (core/update.py:152-160)
-        if (!fuse_lookup) TRY(launch_conv(gemm(conv_desc(ws.corr, ws.ld_corr, ws.ld_corr, nullptr, 0, 0, G[W_CONVC1], W[B_CONVC1], ws.cor1, 256, P, h, w, 256, 1, 1, 1), false, true), s));
-        // convc2 and conv (3 x 3 over 256 channels): tile-resident in two channel passes where the tile-resident layers run (round 6)
-        const bool two_pass = tiles_on && r->opt[MFTX_RAFT_OPT_TILE_CONV2P] != 0 && r->wt[W_CONVC2] && r->wt[W_CONV];
-        auto run_c2 = [&]() -> int {
-            if (two_pass) return launch_tile_conv2p(ws.cor1, 256, r->wt[W_CONVC2], W[B_CONVC2], ws.corflo, 256, 192, P, h, w, r->opt[MFTX_RAFT_OPT_TILE_CELLS], s);
-            return launch_conv(c2, s);
-        };
-        if (forked) {
-            TRY(run_c2());
-            if (hipStreamWaitEvent(s, r->ev_join, 0) != hipSuccess) return fail(MFTX_E_STATE, "raft_refine: join failed");
-        } else if (nopair || AR != MFTX_ARITH_F32) {
-            TRY(run_c2());
-            if (!flow_first && !fuse_flow) TRY(launch_conv(f2, s));
-        } else {
-            TRY(launch_conv_pair(c2, f2, s));      // second layers of the two branches in one launch
-        }
-        if (two_pass) TRY(launch_tile_conv2p(ws.corflo, 256, r->wt[W_CONV], W[B_CONV], ws.hx + 256, 384, 126, P, h, w, r->opt[MFTX_RAFT_OPT_TILE_CELLS], s));
-        else TRY(launch_conv(gemm(conv_desc(ws.corflo, 256, 256, nullptr, 0, 0, G[W_CONV], W[B_CONV], ws.hx + 256, 384, P, h, w, 126, 3, 3, 1), true, true), s));
-        // SepConvGRU (core/update.py:108-123): horizontal 1x5 then vertical 5x1
-        for (int pass = 0; pass < 2; ++pass) {
-            const int kh = pass ? 5 : 1, kw = pass ? 1 : 5;
-            const int szr = pass ? W_ZR2_DYN : W_ZR1_DYN, sq = pass ? W_Q2_DYN : W_Q1_DYN;
-            if (gru_fused) {
-                // the whole pass as ONE kernel (tile_conv.hip: gru_half_kernel): the tile is loaded once, r * h stays in LDS; h goes
-                // hx -> hb in the horizontal pass and back in the vertical one (a tile's halo cells are its neighbours' outputs)
-                GruHalfLaunch g{};
-                g.h_in = pass ? ws.hb : ws.hx; g.ld_hin = pass ? 128 : 384; g.h_out = pass ? ws.hx : ws.hb; g.ld_hout = pass ? 384 : 128;
-                g.mo = ws.hx + 256; g.ld_mo = 384; g.wzr = tile_w(szr); g.wq = tile_w(sq); g.pre_zr = ws.pre_zr[pass]; g.pre_q = ws.pre_q[pass]; g.ctx = ws.ctx;
-                g.z = ws.z; g.hf_in = pass ? ws.hfb : ws.hf; g.hf_out = pass ? ws.hf : ws.hfb; g.P = P; g.h = h; g.w = w; g.pass = pass; g.cells = r->opt[MFTX_RAFT_OPT_TILE_CELLS];
-                TRY(launch_gru_half(g, s));
-                continue;
-            }
-            if (tile_w(szr)) {
-                TileConvLaunch t = tile_layer(ws.hx, 384, ws.hx + 256, 384, tile_w(szr), nullptr, 256, kh, kw, 2);
-                t.addend = ws.pre_zr[pass]; t.ld_addend = 256; t.z = ws.z; t.rh = ws.rh; t.hf = ws.hf; t.ld_hf = 128;
-                TRY(launch_tile_conv(t, s));
-            } else {
-                GruEpilogue g1{1, ws.hx, 384, ws.z, ws.rh, SP ? ws.hf : nullptr, 128};
-                TRY(launch_conv_gru(gemm(conv_desc(ws.hx, 384, 128, ws.hx + 256, 384, 128, G[szr], nullptr, ws.z, 128, P, h, w, 256, kh, kw, 2, 1.f, ws.pre_zr[pass], 256), true, true), g1, s));
-            }
-            if (tile_w(sq)) {
-                TileConvLaunch t = tile_layer(ws.rh, 128, ws.hx + 256, 384, tile_w(sq), nullptr, 128, kh, kw, 3);
-                t.addend = ws.pre_q[pass]; t.ld_addend = 128; t.z = ws.z; t.hf = ws.hf; t.ld_hf = 128; t.hx = ws.hx; t.ld_hx = 384;
-                TRY(launch_tile_conv(t, s));
-            } else {
-                GruEpilogue g2{2, ws.hx, 384, ws.z, ws.rh, SP ? ws.hf : nullptr, 128};
-                TRY(launch_conv_gru(gemm(conv_desc(ws.rh, 128, 128, ws.hx + 256, 384, 128, G[sq], nullptr, ws.hx, 384, P, h, w, 128, kh, kw, 3, 1.f, ws.pre_q[pass], 128), true, true), g2, s));
-            }
-        }
-        // flow head (core/update.py:6-14) and coordinate update (core/raft.py:184)
-        const bool head_fused = tile_w(W_FH1) && r->wproj != nullptr && r->opt[MFTX_RAFT_OPT_FUSE_HEAD] != 0;
-        if (head_fused) {
-            // both layers of the flow head: relu(conv1) stays in LDS, multiplied there with conv2's filter as [256 x 18] partial
-            // products per cell (-> ws.fh, [M][18]); the nine shifted terms are added, and coords1 updated, by a small kernel
-            TileConvLaunch t = tile_layer(ws.hx, 384, nullptr, 0, tile_w(W_FH1), W[B_FH1], 256, 3, 3, 4);
-            t.wproj = r->wproj; t.tout = ws.fh;
-            TRY(launch_tile_conv(t, s));
-            // (the update is left pending for the next iteration's flow-branch kernel when that kernel runs; the last one, and every
-            // one under a debug trace, is applied here -- the last into coords1, whichever buffer is current)
-            const bool defer = !last && fuse_flow && r->opt[MFTX_RAFT_OPT_FUSE_HEAD] != 2 && !r->coords_trace;       // (fuse_flow: the same for every iteration)
-            if (defer) pending = true;
-            else {
-                float *dst = last ? ws.coords1 : ccur;
-                TRY(launch_flow_head_sum(ws.fh, W[B_FH2], ws.delta, ccur, dst, P, h, w, s));
-                ccur = dst;
-            }
-        } else if (tile_w(W_FH1)) {
-            TileConvLaunch t = tile_layer(ws.hx, 384, nullptr, 0, tile_w(W_FH1), W[B_FH1], 256, 3, 3, 1);
-            t.out = ws.fh; t.ldo = 256;
-            TRY(launch_tile_conv(t, s));
-        } else TRY(launch_conv(gemm(conv_desc(ws.hx, 384, 128, nullptr, 0, 0, G[W_FH1], W[B_FH1], ws.fh, 256, P, h, w, 256, 3, 3, 1), true, false), s));
-        // last layer of the flow head, fused with coords1 += delta_flow (core/raft.py:184)
-        if (!head_fused) {
-            const mftx_conv_desc fh2 = conv_desc(ws.fh, 256, 256, nullptr, 0, 0, W[W_FH2], W[B_FH2], ws.delta, 2, P, h, w, 2, 3, 3, 0);
-            if (!conv_small_applicable(fh2)) return fail(MFTX_E_STATE, "raft_refine: flow-head layer does not fit the small-N kernel");
-            TRY(launch_conv_small(fh2, s, ccur, 2));
-        }
-        if (!last) continue;
-        if (r->coords_trace &&       // ... and the final ones (core/raft.py:255-256)
-            hipMemcpyAsync(r->coords_trace + (size_t)iters * M * 2, ccur, (size_t)M * 8, hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return fail(MFTX_E_STATE, "raft_refine: coords trace copy failed");
-        // The upsampling mask is consumed only after the last iteration in test
-        // mode (core/raft.py:190-196,234-239), so it is computed once.
-        // (the hidden 256 channels go to the 1 x 1 layer in split form: a GEMM that splits its A operand in registers runs at half the
-        // matrix utilisation of one that finds it split -- profiles/r4k_pmc_mfma_util.csv: 0.18 against 0.35)
-        if (tile_w(W_MASK0)) {
-            TileConvLaunch t = tile_layer(ws.hx, 384, nullptr, 0, tile_w(W_MASK0), W[B_MASK0], 256, 3, 3, 1);
-            t.out = ws.fh; t.ldo = 256; t.out_split = SP ? 1 : 0;
-            TRY(launch_tile_conv(t, s));
-        } else TRY(launch_conv(gemm(conv_desc(ws.hx, 384, 128, nullptr, 0, 0, G[W_MASK0], W[B_MASK0], ws.fh, 256, P, h, w, 256, 3, 3, 1), true, true), s));
-        TRY(launch_conv(gemm(conv_desc(ws.fh, 256, 256, nullptr, 0, 0, G[W_MASK2], W[B_MASK2], ws.mask, 576, P, h, w, 576, 1, 1, 0, 0.25f), true, false), s));
-        // occlusion + uncertainty heads (core/update.py:196-214)
-        const bool ou_fused = tiles_on && r->wou != nullptr && r->opt[MFTX_RAFT_OPT_FUSE_OU] != 0;
-        if (!ou_fused || r->opt[MFTX_RAFT_OPT_FUSE_OU] == 2) {         // (2: the fused kernel on the materialised input -- A/B, tests)
-            const long long slots = (long long)M * 178;
-            ProfScope prof(PC_GLUE, s, 0);
-            hipLaunchKernelGGL(ou_gather_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, ws.hx,
-                               ws.corr, ws.ld_corr, ccur, ws.delta, ws.ouin, flow_lr, M, h, w, SP ? 1 : 0);
-            TRY(check_launch("ou_gather"));
-        }
-        if (ou_fused) {
-            // both layers of both heads as ONE tile-resident kernel (five channel passes over the 712-channel input, the 3 x 3 x 3 second
-            // layers as a projection epilogue; T -> ws.ouh) + a stencil sum; the input is gathered from its parts by the kernel's loader
-            const OuGather ga{ws.hx, ws.corr, ws.ld_corr, ccur, ws.delta, flow_lr};
-            const bool mat = r->opt[MFTX_RAFT_OPT_FUSE_OU] == 2;
-            TRY(launch_ou_heads(mat ? ws.ouin : nullptr, 712, P, h, w, r->wou, W[B_OU1], r->wouproj, W[B_OU2], ws.ouh, ws.ou, 4, r->opt[MFTX_RAFT_OPT_TILE_CELLS], s,
-                                mat ? nullptr : &ga));
-        } else {
-            TRY(launch_conv(gemm(conv_desc(ws.ouin, 712, 712, nullptr, 0, 0, G[W_OU1], W[B_OU1], ws.ouh, 256, P, h, w, 256, 3, 3, 1), true, false), s));
-            TRY(launch_conv(conv_desc(ws.ouh, 256, 256, nullptr, 0, 0, W[W_OU2], W[B_OU2], ws.ou, 4, P, h, w, 3, 3, 3, 0), s));
-        }
-    }
-    return 0;
-    };   // core
-    if (use_graph) {
-        if (AR == MFTX_ARITH_SPLIT && r->opt[MFTX_RAFT_OPT_FORK] != 0) TRY(ensure_side_stream(r));      // (not while capturing)
+    const RefineCall c{r, r->w, r->wg, plan, s, P, h, w, iters, ws, {ws.lvl[0], ws.lvl[1], ws.lvl[2], ws.lvl[3]},
+                       fmap1, {fmap2, ws.f2l[0], ws.f2l[1], ws.f2l[2]}, flow_lr_out ? flow_lr_out : ws.flow_lr};
+    TRY(c.volume(fmap2, gather));
+    TRY(c.init_state(net, inp, flow_init, gather));
+    if (plan.use_graph) {
+        if (plan.side_stream) TRY(ensure_side_stream(r));        // (not while capturing)
         GraphKey key{};
         key.v[0] = (uintptr_t)P; key.v[1] = (uintptr_t)h; key.v[2] = (uintptr_t)w; key.v[3] = (uintptr_t)iters;
         key.v[4] = reinterpret_cast<uintptr_t>(workspace); key.v[5] = reinterpret_cast<uintptr_t>(flow_lr_out);
-        key.v[6] = (uintptr_t)AR; key.v[7] = reinterpret_cast<uintptr_t>(r->wfused); key.v[8] = reinterpret_cast<uintptr_t>(s);
+        key.v[6] = (uintptr_t)r->arith; key.v[7] = reinterpret_cast<uintptr_t>(r->wfused); key.v[8] = reinterpret_cast<uintptr_t>(s);
         key.v[9] = reinterpret_cast<uintptr_t>(r->wflow); key.v[10] = reinterpret_cast<uintptr_t>(r->wt[W_ZR1_DYN]); key.v[11] = reinterpret_cast<uintptr_t>(r->wproj);
-        key.v[12] = reinterpret_cast<uintptr_t>(r->wou); key.v[13] = ctx_supplied ? 1 : 0;       // (with the parts supplied the sequence is four launches shorter)
-        TRY(r->graphs->run(key, s, core));
-    } else {
-        TRY(core());
-    }
-    return launch_convex_upsample(flow_lr, ws.ou, 4, ws.mask, P, h, w, pad_left, pad_right, pad_top, pad_bottom,
+        key.v[12] = reinterpret_cast<uintptr_t>(r->wou); key.v[13] = plan.ctx_supplied ? 1 : 0;         // (with the parts supplied the sequence is four launches shorter)
+        TRY(r->graphs->run(key, s, [&c]() { return c.core(); }));
+    } else TRY(c.core());
+    return launch_convex_upsample(c.flow_lr, ws.ou, 4, ws.mask, P, h, w, pad_left, pad_right, pad_top, pad_bottom,
                                   flow, occl, sigma, packed, s, r->nonfinite);
 }
 
@@ -873,7 +881,10 @@ extern "C" int mftx_raft_frame_prepare(mftx_raft *r, int h, int w, const float *
         TRY(check_launch("split_rows"));
     }
     float *const zr[2] = {ctx_zr1, ctx_zr2}, *const q[2] = {ctx_q1, ctx_q2};
-    return launch_context_parts(r, r->opt[MFTX_RAFT_OPT_TILE_CONV] == 2, true, inps, 128, 1, h, w, zr, q, s);
+    RefinePlan plan{};           // (what context_parts reads of it; the checks above pin both)
+    plan.SP = true; plan.tiles_on = r->opt[MFTX_RAFT_OPT_TILE_CONV] == 2;
+    const RefineCall c{r, r->w, r->wg, plan, s, 1, h, w};
+    return c.context_parts(inps, 128, zr, q);
 }
 
 extern "C" int mftx_volume_query_split(const float *in, void *out, long long n_floats, void *stream) {

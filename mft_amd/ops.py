@@ -1010,6 +1010,19 @@ class RaftEngine:
                  "iterations": [{"coords": to_map(trace[i])} for i in range(iters + 1)]}
         return out, debug
 
+    PLAN_FIELDS = ("presplit", "fuse_lookup", "tiles_on", "gru_fused", "ctx_supplied", "two_pass", "flow", "pair_second", "head_fused",
+                   "defer_update", "ou_fused", "ou_materialised", "use_graph", "side_stream")      # mftx_raft_plan's order
+    FLOW_SCHEDULES = ("fused", "side", "first", "after_lookup", "with_lookup")                    # MFTX_FLOW_*
+
+    def plan(self, P, h, w, ctx_supplied=False):
+        """The launch schedule ``refine`` would run for P pairs of h x w cells (``mftx_raft_plan``; launches nothing): a dict of
+        PLAN_FIELDS -> bool, and "flow" -> one of FLOW_SCHEDULES."""
+        out = (C.c_int * len(self.PLAN_FIELDS))()
+        check(_lib.load().mftx_raft_plan(self._h, P, h, w, int(bool(ctx_supplied)), out, len(out)), "mftx_raft_plan")
+        plan = {k: bool(v) for k, v in zip(self.PLAN_FIELDS, out)}
+        plan["flow"] = self.FLOW_SCHEDULES[out[self.PLAN_FIELDS.index("flow")]]
+        return plan
+
     def graph_stats(self):
         """(graphs captured, graph launches) of this handle (``mftx_raft_graph_stats``)."""
         c, r = C.c_ulonglong(), C.c_ulonglong()
@@ -1119,44 +1132,32 @@ class RaftEngine:
         if packed is not None and tuple(packed.shape) != (P, H0, W0, 4):
             raise MftxError("packed must be [P, H0, W0, 4]")
         ws = self.workspace(P, h, w)
+
+        def tail():      # flow_init ... stream: what every entry point takes behind the maps (evaluated in argument order)
+            return (_chk(flow_init, "flow_init") if flow_init is not None else None, pl, pr, pt, pb,
+                    flow.data_ptr() if planar else None, occl.data_ptr() if planar else None, sigma.data_ptr() if planar else None,
+                    _chk(packed, "packed") if packed is not None else None, flow_lr.data_ptr() if want_flow_lr else None,
+                    ws.data_ptr(), ws.numel(), _stream())
+
         if gathered:
             if not self.can_gather(P) or not (len(fmap2) == len(net) == len(inp) == P):
                 raise MftxError("refine: per-pair map lists need the split arithmetic with the tile-resident volume and P <= 16")
             arrs = [_lib.ptr_array([_chk(t, "map") for t in lst]) for lst in (fmap1, fmap2, net, inp)]
+            maps = [a[0] for a in arrs]
             if prepared:
                 ctx, f1s, f2s = prepared.get("ctx"), prepared.get("f1s"), prepared.get("f2s")
                 if (ctx is not None and len(ctx) != P) or (f1s is not None and len(f1s) != P):
                     raise MftxError("refine: prepared parts for every pair, or none")
                 carr = _lib.ptr_array([_chk(t, "context part") for parts in ctx for t in parts]) if ctx is not None else (None, None)
                 sarr = _lib.ptr_array([_chk(t, "split map") for t in f1s]) if f1s is not None else (None, None)
-                check(lib.mftx_raft_refine_gather_ex(self._h, P, h, w, iters, arrs[0][0], arrs[1][0], arrs[2][0], arrs[3][0],
-                                                     carr[0], sarr[0], _chk(f2s, "split map") if f2s is not None else None,
-                                                     _chk(flow_init, "flow_init") if flow_init is not None else None,
-                                                     pl, pr, pt, pb,
-                                                     flow.data_ptr() if planar else None, occl.data_ptr() if planar else None,
-                                                     sigma.data_ptr() if planar else None,
-                                                     _chk(packed, "packed") if packed is not None else None,
-                                                     flow_lr.data_ptr() if want_flow_lr else None,
-                                                     ws.data_ptr(), ws.numel(), _stream()), "mftx_raft_refine_gather_ex")
-                return (flow, occl, sigma, flow_lr) if want_flow_lr else (flow, occl, sigma)
-            check(lib.mftx_raft_refine_gather(self._h, P, h, w, iters, arrs[0][0], arrs[1][0], arrs[2][0], arrs[3][0],
-                                              _chk(flow_init, "flow_init") if flow_init is not None else None,
-                                              pl, pr, pt, pb,
-                                              flow.data_ptr() if planar else None, occl.data_ptr() if planar else None,
-                                              sigma.data_ptr() if planar else None,
-                                              _chk(packed, "packed") if packed is not None else None,
-                                              flow_lr.data_ptr() if want_flow_lr else None,
-                                              ws.data_ptr(), ws.numel(), _stream()), "mftx_raft_refine_gather")
-            return (flow, occl, sigma, flow_lr) if want_flow_lr else (flow, occl, sigma)
-        if prepared:
+                check(lib.mftx_raft_refine_gather_ex(self._h, P, h, w, iters, *maps, carr[0], sarr[0],
+                                                     _chk(f2s, "split map") if f2s is not None else None, *tail()),
+                      "mftx_raft_refine_gather_ex")
+            else:
+                check(lib.mftx_raft_refine_gather(self._h, P, h, w, iters, *maps, *tail()), "mftx_raft_refine_gather")
+        elif prepared:
             raise MftxError("refine: prepared parts go with per-pair map lists")
-        check(lib.mftx_raft_refine(self._h, P, h, w, iters, _chk(fmap1, "fmap1"), _chk(fmap2, "fmap2"),
-                                   _chk(net, "net"), _chk(inp, "inp"),
-                                   _chk(flow_init, "flow_init") if flow_init is not None else None,
-                                   pl, pr, pt, pb,
-                                   flow.data_ptr() if planar else None, occl.data_ptr() if planar else None,
-                                   sigma.data_ptr() if planar else None,
-                                   _chk(packed, "packed") if packed is not None else None,
-                                   flow_lr.data_ptr() if want_flow_lr else None,
-                                   ws.data_ptr(), ws.numel(), _stream()), "mftx_raft_refine")
+        else:
+            check(lib.mftx_raft_refine(self._h, P, h, w, iters, _chk(fmap1, "fmap1"), _chk(fmap2, "fmap2"),
+                                       _chk(net, "net"), _chk(inp, "inp"), *tail()), "mftx_raft_refine")
         return (flow, occl, sigma, flow_lr) if want_flow_lr else (flow, occl, sigma)

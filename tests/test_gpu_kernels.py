@@ -947,12 +947,13 @@ def test_lookup_convc1_argument_errors(ops_mod):
 
 
 
-def _engine_outputs(options, P=3, h=24, w=40, iters=4):
-    """One refinement of the RAFT engine on seeded random features with the given per-handle options."""
+def _engine_outputs(options, P=3, h=24, w=40, iters=4, arith=None):
+    """One refinement of the RAFT engine on seeded random features with the given per-handle options (arith: ops.ARITH_*, default
+    the engine's)."""
     from mft_amd import ops
     from mft_amd.weights import make_weights
     sd = {k: torch.from_numpy(v).cuda() for k, v in make_weights(7).items()}
-    eng = ops.RaftEngine(sd, "cuda", options=options)
+    eng = ops.RaftEngine(sd, "cuda", options=options, **({} if arith is None else {"arith": arith}))
     g = torch.Generator().manual_seed(11)
     f1 = torch.randn(P, h * w, 256, generator=g).cuda()
     f2 = (f1.cpu() + 0.3 * torch.randn(P, h * w, 256, generator=g)).cuda()
@@ -1341,6 +1342,22 @@ def test_engine_deferred_flow_head_update_bitwise():
     merged, own = _engine_outputs({"tile_conv": 2}), _engine_outputs({"tile_conv": 2, "fuse_head": 2})
     assert np.isfinite(merged).all()
     assert np.array_equal(merged, own)
+
+
+def test_engine_flow_branch_schedules_bitwise():
+    """The motion encoder's unfused flow branch wherever the schedule puts it (RaftEngine.plan: "flow"; tests/test_refine_plan.py
+    holds the options to the schedules named here).  Split arithmetic: the same two kernels on the side stream (fork = -1),
+    behind the fused lookup (0) and in front of it (2).  fp32 MFMA: the grouped launches -- lookup + convf1, convc2 + convf2:
+    same tiles, same results -- against one launch per layer (group = 0).  The same bits.  P = 2, 24 x 40 cells: ragged tiles
+    in both directions."""
+    from mft_amd import ops
+    args = (2, 24, 40, 3)
+    side, after, first = (_engine_outputs({"fuse_flow": 0, "tile_conv": 2, "fork": fork}, *args) for fork in (-1, 0, 2))
+    grouped, apart = (_engine_outputs({"group": g}, *args, arith=ops.ARITH_F32) for g in (1, 0))
+    assert np.isfinite(side).all() and np.isfinite(grouped).all()
+    for tag, a, b in (("fork 0 vs -1", after, side), ("fork 2 vs -1", first, side), ("fp32 group 1 vs 0", grouped, apart)):
+        print(f"{tag}: max |difference| {np.abs(a - b).max():.3e}")
+        assert np.array_equal(a, b), tag
 
 
 def test_engine_refine_gather_bitwise():
