@@ -438,6 +438,24 @@ void mftx_encoder_destroy(mftx_encoder *e);
 size_t mftx_encoder_workspace_bytes(int H0, int W0);
 int mftx_encoder_forward(mftx_encoder *e, const uint8_t *img, int H0, int W0, float *out0, float *out1,
                          void *workspace, size_t workspace_bytes, void *stream);
+/* Two steps of mftx_encoder_forward on their own (tests, tools): the same launch code, so what they compute is what the
+ * engine computes.
+ * mftx_encoder_prep: the pre-processing kernel.  img as above (H0, W0 >= 1); out: fp32 [Hp][Wp + 6][4], 16-byte aligned, with
+ * Hp x Wp the frame padded to multiples of 8 (InputPadder 'sintel': the smaller half of an axis' pad, pad / 2, goes left / top,
+ * replicated border pixels).  Padded pixel (y, x) lies at out[y][x + 3] = (R, G, B, 0) with v -> 2 (v / 255) - 1; the three
+ * columns on either side and the 4th channel are zero (the stem's 7-pixel windows read them as its zero padding).
+ * mftx_instance_norm: nn.InstanceNorm2d (no affine, eps 1e-5, biased variance) of a pixel-major map x [rows][C], in place;
+ * C a multiple of 8 in 8..256.  Statistics in fp64 with a fixed summation order (the same bits on every run), then
+ *   mode 0: x = relu(n(x));  mode 1: x = relu(res + relu(n(x))), res [rows][C] required;  mode 2: x = n(x).
+ * split != 0: x is WRITTEN in split form (mftx_conv_desc.a_split) and res is READ in split form; x and res then 32-byte
+ * aligned, else 16.  A NaN in a channel makes that channel NaN and leaves the others alone.  workspace:
+ * mftx_instance_norm_workspace_bytes(C) bytes (0 for a C it refuses), 16-byte aligned.  Refused before any launch: null
+ * pointers, rows <= 0, a bad C or mode, mode 1 without res (MFTX_E_ARG), misaligned pointers (MFTX_E_ALIGN), a workspace
+ * that is too small (MFTX_E_WORKSPACE). */
+int mftx_encoder_prep(const uint8_t *img, int H0, int W0, float *out, void *stream);
+size_t mftx_instance_norm_workspace_bytes(int C);
+int mftx_instance_norm(float *x, int rows, int C, const float *res, int mode, int split, void *workspace,
+                       size_t workspace_bytes, void *stream);
 
 /* ---- a10 + a12: convex 8x upsampling + post-processing ---------------------
  * Replaces RAFT.upsample_flow (core/raft.py:83-94) for the three heads and

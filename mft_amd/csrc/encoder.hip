@@ -157,6 +157,53 @@ __global__ __launch_bounds__(256) void instnorm_apply_kernel(float *__restrict__
     }
 }
 
+#define TRY(expr) do { int _e = (expr); if (_e) return _e; } while (0)
+
+// ---------------------------------------------------------------------------
+// launch helpers: the engine and the per-op exports (mftx_encoder_prep, mftx_instance_norm) go through the same code
+// ---------------------------------------------------------------------------
+// InputPadder(mode='sintel') (core/utils/utils.py:9-19): replicate pad to multiples of 8, the smaller half left / top
+struct EncPad { int Hp, Wp, pl, pt; };
+static EncPad enc_pad(int H0, int W0) {
+    const int ph = (((H0 / 8) + 1) * 8 - H0) % 8, pw = (((W0 / 8) + 1) * 8 - W0) % 8;
+    return EncPad{H0 + ph, W0 + pw, pw / 2, ph / 2};
+}
+
+static int launch_enc_prep(const uint8_t *img, int H0, int W0, float *out, hipStream_t s) {
+    const EncPad p = enc_pad(H0, W0);
+    {
+        ProfScope prof(PC_GLUE, s, 0);
+        hipLaunchKernelGGL(enc_prep_kernel, dim3(cdiv(p.Wp + 6, 256), p.Hp), dim3(256), 0, s, img, H0, W0, p.pl, p.pt, p.Hp, p.Wp, out);
+    }
+    return check_launch("enc_prep");
+}
+
+// statistics (partial sums, finalize) + apply, in place on x [rows][C]; part: IN_SLABS * C * 2 doubles, stat: C * 2 floats
+static int launch_instance_norm(float *x, int rows, int C, const float *res, int mode, int split, double *part, float *stat,
+                                hipStream_t s) {
+    {
+        ProfScope prof(PC_ENC_NORM, s, 4.0 * rows * C);
+        hipLaunchKernelGGL(instnorm_partial_kernel, dim3(IN_SLABS), dim3(256), 0, s, x, rows, C, part);
+    }
+    TRY(check_launch("instnorm_partial"));
+    {
+        ProfScope prof(PC_ENC_NORM, s, 0);
+        hipLaunchKernelGGL(instnorm_finalize_kernel, dim3(cdiv(C, 16)), dim3(256), 0, s, part, rows, C, stat);
+    }
+    TRY(check_launch("instnorm_finalize"));
+    const long long n8 = (long long)rows * C / 8;
+    const int blocks = (int)std::min<long long>((n8 + 255) / 256, 4096);
+    {
+        ProfScope prof(PC_ENC_NORM, s, (mode == 1 ? 12.0 : 8.0) * rows * C);
+        hipLaunchKernelGGL(instnorm_apply_kernel, dim3(blocks), dim3(256), 0, s, x, rows, C, stat, res, mode, split ? 1 : 0);
+    }
+    return check_launch("instnorm_apply");
+}
+
+// workspace of mftx_instance_norm: the partial sums, then (256-byte aligned) the per-channel statistics
+static size_t instnorm_part_bytes(int C) { return ((size_t)IN_SLABS * C * 2 * sizeof(double) + 255) & ~size_t(255); }
+static size_t instnorm_ws_bytes(int C) { return instnorm_part_bytes(C) + (size_t)C * 2 * sizeof(float); }
+
 // ---------------------------------------------------------------------------
 // engine
 // ---------------------------------------------------------------------------
@@ -258,8 +305,6 @@ extern "C" size_t mftx_encoder_workspace_bytes(int H0, int W0) {
     return enc_carve(nullptr, Hp, Wp).bytes;
 }
 
-#define TRY(expr) do { int _e = (expr); if (_e) return _e; } while (0)
-
 namespace {
 struct Enc {
     const mftx_encoder *e;
@@ -282,23 +327,7 @@ struct Enc {
     }
     bool SP() const { return e->arith == MFTX_ARITH_SPLIT; }
     int norm(float *x, int rows, int C, int mode, const float *res = nullptr) {
-        {
-            ProfScope prof(PC_ENC_NORM, s, 4.0 * rows * C);
-            hipLaunchKernelGGL(instnorm_partial_kernel, dim3(IN_SLABS), dim3(256), 0, s, x, rows, C, ws.part);
-        }
-        TRY(check_launch("instnorm_partial"));
-        {
-            ProfScope prof(PC_ENC_NORM, s, 0);
-            hipLaunchKernelGGL(instnorm_finalize_kernel, dim3(cdiv(C, 16)), dim3(256), 0, s, ws.part, rows, C, ws.stat);
-        }
-        TRY(check_launch("instnorm_finalize"));
-        const long long n8 = (long long)rows * C / 8;
-        const int blocks = (int)std::min<long long>((n8 + 255) / 256, 4096);
-        {
-            ProfScope prof(PC_ENC_NORM, s, (mode == 1 ? 12.0 : 8.0) * rows * C);
-            hipLaunchKernelGGL(instnorm_apply_kernel, dim3(blocks), dim3(256), 0, s, x, rows, C, ws.stat, res, mode, SP() ? 1 : 0);
-        }
-        return check_launch("instnorm_apply");
+        return launch_instance_norm(x, rows, C, res, mode, SP() ? 1 : 0, ws.part, ws.stat, s);
     }
     // one residual block (core/extractor.py:6-62); x: [hin*win][cin] -> out: [h*w][planes]; tmp, sc scratch
     int block(int c1, int c2, int ds, const float *x, int cin, int hin, int win, float *tmp, float *sc, float *out,
@@ -339,8 +368,7 @@ extern "C" int mftx_encoder_forward(mftx_encoder *e, const uint8_t *img, int H0,
     if (!img || !out0 || !workspace || (!e->instance_norm && !out1)) return fail(MFTX_E_ARG, "encoder_forward: null pointer");
     if (H0 < 16 || W0 < 16) return fail(MFTX_E_ARG, "encoder_forward: image too small");
     if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(MFTX_E_ALIGN, "encoder_forward: workspace must be 256-byte aligned");
-    const int ph = (((H0 / 8) + 1) * 8 - H0) % 8, pw = (((W0 / 8) + 1) * 8 - W0) % 8;
-    const int Hp = H0 + ph, Wp = W0 + pw, pl = pw / 2, pt = ph / 2;
+    const int Hp = enc_pad(H0, W0).Hp, Wp = enc_pad(H0, W0).Wp;
     Enc E{e, enc_carve(workspace, Hp, Wp), (hipStream_t)stream};
     if (E.ws.bytes > workspace_bytes) return fail(MFTX_E_WORKSPACE, "encoder_forward: workspace %zu < %zu", workspace_bytes, E.ws.bytes);
     const bool graphs_on = e->graphs && e->use_graph && !prof_enabled();
@@ -351,11 +379,7 @@ extern "C" int mftx_encoder_forward(mftx_encoder *e, const uint8_t *img, int H0,
     }
     struct Leave { GraphCache *g; bool on; ~Leave() { if (on) g->proxy.leave(nullptr); } } leave{e->graphs, proxied};
     hipStream_t s = E.s;
-    {
-        ProfScope prof(PC_GLUE, s, 0);
-        hipLaunchKernelGGL(enc_prep_kernel, dim3(cdiv(Wp + 6, 256), Hp), dim3(256), 0, s, img, H0, W0, pl, pt, Hp, Wp, E.ws.img);
-    }
-    TRY(check_launch("enc_prep"));
+    TRY(launch_enc_prep(img, H0, W0, E.ws.img, s));
     // From the stem to the last residual block the layers touch the workspace only: one hipGraph per (size, workspace,
     // stream), see graph_cache.h; the pre-processing kernel (reads the caller's image) and the head (writes the caller's
     // maps) are launched plainly around it.
@@ -399,4 +423,36 @@ extern "C" int mftx_encoder_forward(mftx_encoder *e, const uint8_t *img, int H0,
     if (e->instance_norm) return E.conv(EC_HEAD, E.ws.a, 128, 128, h3, w3, out0, 256, 256, h3, w3, 1, 1, 0, nullptr, true);
     TRY(E.conv(EC_HEAD, E.ws.a, 128, 128, h3, w3, out0, 128, 128, h3, w3, 1, 1, 3));   // net = tanh(first 128)
     return E.conv(EC_HEAD2, E.ws.a, 128, 128, h3, w3, out1, 128, 128, h3, w3, 1, 1, 1);  // inp = relu(last 128)
+}
+
+// the pre-processing kernel alone, launched as mftx_encoder_forward launches it
+extern "C" int mftx_encoder_prep(const uint8_t *img, int H0, int W0, float *out, void *stream) {
+    if (!img || !out) return fail(MFTX_E_ARG, "encoder_prep: null pointer");
+    if (H0 < 1 || W0 < 1) return fail(MFTX_E_ARG, "encoder_prep: empty image");
+    if (!aligned16(out)) return fail(MFTX_E_ALIGN, "encoder_prep: out must be 16-byte aligned");
+    return launch_enc_prep(img, H0, W0, out, (hipStream_t)stream);
+}
+
+extern "C" size_t mftx_instance_norm_workspace_bytes(int C) {
+    if (C < 8 || C > 256 || C % 8) return 0;
+    return instnorm_ws_bytes(C);
+}
+
+// the encoders' normalisation pass alone: what Enc::norm runs
+extern "C" int mftx_instance_norm(float *x, int rows, int C, const float *res, int mode, int split, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+    if (!x || !workspace) return fail(MFTX_E_ARG, "instance_norm: null pointer");
+    if (rows <= 0) return fail(MFTX_E_ARG, "instance_norm: rows must be positive");
+    if (C < 8 || C > 256 || C % 8) return fail(MFTX_E_ARG, "instance_norm: C must be a multiple of 8 in 8..256");
+    if (mode < 0 || mode > 2) return fail(MFTX_E_ARG, "instance_norm: mode must be 0, 1 or 2");
+    if (mode == 1 && !res) return fail(MFTX_E_ARG, "instance_norm: mode 1 adds a residual map");
+    const uintptr_t mask = split ? 31 : 15;          // split-form rows are 32-byte groups (mftx_conv_desc.a_split)
+    if ((reinterpret_cast<uintptr_t>(x) & mask) || (mode == 1 && (reinterpret_cast<uintptr_t>(res) & mask)))
+        return fail(MFTX_E_ALIGN, "instance_norm: maps must be %d-byte aligned", (int)mask + 1);
+    if (!aligned16(workspace)) return fail(MFTX_E_ALIGN, "instance_norm: workspace must be 16-byte aligned");
+    if (workspace_bytes < instnorm_ws_bytes(C))
+        return fail(MFTX_E_WORKSPACE, "instance_norm: workspace %zu < %zu", workspace_bytes, instnorm_ws_bytes(C));
+    double *part = static_cast<double *>(workspace);
+    float *stat = reinterpret_cast<float *>(static_cast<char *>(workspace) + instnorm_part_bytes(C));
+    return launch_instance_norm(x, rows, C, mode == 1 ? res : nullptr, mode, split, part, stat, (hipStream_t)stream);
 }

@@ -274,6 +274,35 @@ class EncoderEngine:
         return outs
 
 
+def encoder_prep(img_u8: torch.Tensor) -> torch.Tensor:
+    """The encoders' pre-processing kernel alone (``mftx_encoder_prep``): uint8 [H0, W0, 3] BGR on the device ->
+    fp32 [Hp, Wp + 6, 4]: RGB0 of the replicate-padded frame as 2 (v / 255) - 1, three zero columns on either side."""
+    lib = _lib.load()
+    if img_u8.dim() != 3 or img_u8.shape[2] != 3:
+        raise MftxError("encoder_prep: img must be [H0, W0, 3]")
+    H0, W0 = int(img_u8.shape[0]), int(img_u8.shape[1])
+    Hp, Wp = -(-H0 // 8) * 8, -(-W0 // 8) * 8
+    out = torch.empty(Hp, Wp + 6, 4, dtype=torch.float32, device=img_u8.device)
+    check(lib.mftx_encoder_prep(_chk(img_u8, "img", torch.uint8), H0, W0, out.data_ptr(), _stream()), "mftx_encoder_prep")
+    return out
+
+
+def instance_norm(x: torch.Tensor, mode: int, res: torch.Tensor = None, split: bool = False) -> torch.Tensor:
+    """The encoders' normalisation pass alone (``mftx_instance_norm``), IN PLACE on x [rows, C] (returned): mode 0
+    relu(n(x)), 1 relu(res + relu(n(x))), 2 n(x).  split: x is written -- and res read -- in split form."""
+    lib = _lib.load()
+    if x.dim() != 2:
+        raise MftxError("instance_norm: x must be [rows, C]")
+    rows, Cc = int(x.shape[0]), int(x.shape[1])
+    if res is not None and tuple(res.shape) != (rows, Cc):
+        raise MftxError("instance_norm: res must have the shape of x")
+    need = lib.mftx_instance_norm_workspace_bytes(Cc)
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+    check(lib.mftx_instance_norm(_chk(x, "x"), rows, Cc, _chk(res, "res") if res is not None else None, int(mode),
+                                 int(bool(split)), ws.data_ptr(), ws.numel(), _stream()), "mftx_instance_norm")
+    return x
+
+
 # ---------------------------------------------------------------------------
 # per-op wrappers
 # ---------------------------------------------------------------------------
@@ -551,15 +580,17 @@ def corr_lookup_ondemand(f1: torch.Tensor, f2_levels, coords: torch.Tensor, h: i
 
 def conv2d(x: torch.Tensor, wpk: torch.Tensor, bias, P, h, w, N, kh, kw, act=None, out_scale=1.0, x2=None,
            addend=None, stride=0, hin=0, win=0, pad_y=0, pad_x=0, residual_mode=0, arith=ARITH_F32, a_split=False,
-           out_split=False, out=None, tile=None):
+           out_split=False, out=None, tile=None, lda0=None, c0=None):
     """x: pixel-major [P*h*w, C0] (optionally concatenated with x2 [P*h*w, C1]) ->
     [P*h*w, N].  arith = ARITH_SPLIT: wpk is the output of ``split_weights``.  tile: force the workgroup tile shape
-    (``mftx_conv2d_tile``; tests and micro-benchmarks -- every shape gives the same bits)."""
+    (``mftx_conv2d_tile``; tests and micro-benchmarks -- every shape gives the same bits).  lda0 / c0: row stride and
+    channel count of x instead of ``x.shape[1]`` -- overlapping windows, as the encoders' stem reads its input: 28 floats
+    (7 pixels x RGB0) every 4 floats (lda0 = 4, c0 = 28, kh = 7, kw = 1, pad_x = -1; csrc/encoder.hip)."""
     lib = _lib.load()
     if out is None:
         out = torch.empty(P * h * w, N, dtype=torch.float32, device=x.device)
     d = ConvDesc()
-    d.a0, d.lda0, d.c0 = _chk(x, "x"), x.shape[1], x.shape[1]
+    d.a0, d.lda0, d.c0 = _chk(x, "x"), x.shape[1] if lda0 is None else int(lda0), x.shape[1] if c0 is None else int(c0)
     if x2 is not None:
         d.a1, d.lda1, d.c1 = _chk(x2, "x2"), x2.shape[1], x2.shape[1]
     else:

@@ -145,7 +145,7 @@ def _norm(x, sd, name, kind):
                         sd[name + ".weight"], sd[name + ".bias"], training=False, eps=1e-5)
 
 
-def _res_block(x, sd, p, kind, stride):
+def _res_block(x, sd, p, kind, stride, shortcuts=None):
     y = F.conv2d(x, sd[p + ".conv1.weight"], sd[p + ".conv1.bias"], stride=stride, padding=1)
     y = F.relu(_norm(y, sd, p + ".norm1", kind))
     y = F.conv2d(y, sd[p + ".conv2.weight"], sd[p + ".conv2.bias"], padding=1)
@@ -153,18 +153,34 @@ def _res_block(x, sd, p, kind, stride):
     if stride != 1:
         x = F.conv2d(x, sd[p + ".downsample.0.weight"], sd[p + ".downsample.0.bias"], stride=stride)
         x = _norm(x, sd, p + ".downsample.1" if kind == "batch" else p + ".norm3", kind)
+        if shortcuts is not None:
+            shortcuts[p.split(".", 1)[1]] = x
     return F.relu(x + y)
+
+
+ENCODER_STAGES = ("stem", "layer1.0", "layer1.1", "layer2.0", "layer2.1", "layer3.0", "layer3.1", "head")
+
+
+def encoder_stages(x, sd, prefix, kind, shortcuts=None):
+    """The eight maps BasicEncoder.forward passes through, in ``ENCODER_STAGES`` order: the stem after its norm and ReLU, the
+    six residual blocks, the 1x1 head.  shortcuts (optional dict): receives the normalised shortcut branch of the first block of
+    each stride-2 stage under "layer2.0" / "layer3.0".  Works in fp64 inside ``precision(torch.float64)`` with ``cast_weights``."""
+    x = F.conv2d(x, sd[prefix + ".conv1.weight"], sd[prefix + ".conv1.bias"], stride=2, padding=3)
+    x = F.relu(_norm(x, sd, prefix + ".norm1", kind))
+    stages = [x]
+    for li, stride in ((1, 1), (2, 2), (3, 2)):
+        x = _res_block(x, sd, f"{prefix}.layer{li}.0", kind, stride, shortcuts)
+        stages.append(x)
+        x = _res_block(x, sd, f"{prefix}.layer{li}.1", kind, 1)
+        stages.append(x)
+    stages.append(F.conv2d(x, sd[prefix + ".conv2.weight"], sd[prefix + ".conv2.bias"]))
+    return stages
 
 
 def encoder(x, sd, prefix, kind):
     """BasicEncoder.forward: 7x7/2 conv, norm, relu, 3 stages of 2 residual
     blocks (64 s1, 96 s2, 128 s2), 1x1 conv to 256 (core/extractor.py:168-195)."""
-    x = F.conv2d(x, sd[prefix + ".conv1.weight"], sd[prefix + ".conv1.bias"], stride=2, padding=3)
-    x = F.relu(_norm(x, sd, prefix + ".norm1", kind))
-    for li, stride in ((1, 1), (2, 2), (3, 2)):
-        x = _res_block(x, sd, f"{prefix}.layer{li}.0", kind, stride)
-        x = _res_block(x, sd, f"{prefix}.layer{li}.1", kind, 1)
-    return F.conv2d(x, sd[prefix + ".conv2.weight"], sd[prefix + ".conv2.bias"])
+    return encoder_stages(x, sd, prefix, kind)[-1]
 
 
 def normalise_image(x):
