@@ -2,14 +2,16 @@
 """Track every pixel of a video with MFT and write the point / edit overlays -- the reference's ``demo.py`` on
 the MI355X engine.
 
-    python demo.py --video <dir of PNG frames | frames.npy> [--edit edit.png] [--out demo_out/] [--synthetic] [--gpu-overlays]
+    python demo.py --video <dir of PNG frames | frames.npy> [--edit edit.png] [--out demo_out/] [--synthetic] [--gpu-overlays | --track-store]
 
 Differences forced by the environment: no OpenCV here, so the input is a directory of PNG frames or a ``.npy``
 frame array (video containers work when cv2 is importable) and the overlays are written as numbered PNGs instead of
 an mp4; ``--synthetic`` tracks the seeded synthetic video with seeded stand-in weights (no checkpoint ships with
 this build).  Frames go to the GPU through a pinned upload ring (``mft_amd/video.py:FrameRing``).  With ``--gpu-overlays``
 both overlays are rendered on the GPU inside the tracking loop (``mft_amd/vis.py:DeviceOverlay``) and written as they
-arrive: no dense result is downloaded or kept.
+arrive: no dense result is downloaded or kept.  With ``--track-store`` the tracker keeps every frame's dense result on the GPU in
+16 bits (``mft_amd/trackstore.py``: 8 bytes per pixel) and nothing is downloaded inside the loop; afterwards ONE read-out gives the
+points of all frames, and the edit overlay is drawn from the stored frames.
 """
 import argparse
 import logging
@@ -41,6 +43,7 @@ def parse_arguments():
     ap.add_argument('--synthetic', type=int, default=0, metavar='N', help='track N frames of the seeded synthetic video')
     ap.add_argument('--synthetic_weights_seed', type=int, default=None, help='run on seeded stand-in weights')
     ap.add_argument('--gpu-overlays', action='store_true', help='render the overlays on the GPU while tracking; dense results stay on the device')
+    ap.add_argument('--track-store', action='store_true', help='keep every dense result on the GPU in 16 bits; read the points out after the pass')
     return ap.parse_args()
 
 
@@ -52,6 +55,10 @@ def run(args):
         config.flow_config.model = None
         config.flow_config.synthetic_weights_seed = args.synthetic_weights_seed or 0
     config.keep_result_on_device = True
+    if args.track_store:
+        if args.gpu_overlays:
+            raise SystemExit("--track-store and --gpu-overlays are two ways to avoid the per-frame download: choose one")
+        config.track_store = True
     tracker = config.tracker_class(config)
     if args.synthetic:
         from mft_amd.synth import SyntheticVideo
@@ -64,6 +71,8 @@ def run(args):
     logger.info("tracking %d frames", len(frames))
     if args.gpu_overlays:
         return run_gpu_overlays(args, tracker, frames, name)
+    if args.track_store:
+        return run_track_store(args, tracker, frames, name)
     from mft_amd.results import FlowOUTrackingResult
     results, host_results, queries = [], [], None
     drain = vio.ResultDrain()
@@ -89,6 +98,30 @@ def run(args):
         vio.imwrite_bgr(args.out / f"{name}_points" / f"{i:05d}.png", vis.draw_dots(frame, coords, occlusions))
         if edit is not None:
             vio.imwrite_bgr(args.out / f"{name}_edit" / f"{i:05d}.png", vis.draw_edit(frame, result, edit))
+    logger.info("wrote %s", args.out)
+    return 0
+
+
+def run_track_store(args, tracker, frames, name):
+    """The tracker keeps the dense results (``config.track_store``): the loop only tracks.  Afterwards one ``tracks()`` call reads
+    the query grid out of all stored frames, and ``store.result(i)`` dequantises a frame on the device for the edit overlay."""
+    up = [torch.cuda.current_stream()]
+    if getattr(tracker.flower, "_enc_stream", None) is not None:
+        up.append(tracker.flower._enc_stream)
+    for i, dev_frame in enumerate(vio.FrameRing(frames, streams=up)):
+        if i == 0:
+            tracker.init(dev_frame)
+        else:
+            tracker.track(dev_frame)
+    store = tracker.track_store
+    logger.info("track store: %d frames, %.1f MB on the device", len(store), store.nbytes / 1e6)
+    queries = vis.get_queries(frames[0].shape[:2], args.grid_spacing)
+    coords, occlusions = store.tracks(queries, frames=range(len(frames)))
+    edit = vio.imread_unchanged(args.edit) if args.edit.exists() else None
+    for i, frame in enumerate(frames):
+        vio.imwrite_bgr(args.out / f"{name}_points" / f"{i:05d}.png", vis.draw_dots(frame, coords[:, i], occlusions[:, i]))
+        if edit is not None:
+            vio.imwrite_bgr(args.out / f"{name}_edit" / f"{i:05d}.png", vis.draw_edit(frame, store.result(i), edit))
     logger.info("wrote %s", args.out)
     return 0
 

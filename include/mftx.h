@@ -586,6 +586,46 @@ int mftx_quantize_u16(const float *x, long long n, uint16_t *q, float *lohi,
                       void *workspace, size_t workspace_bytes, void *stream);
 int mftx_dequantize_u16(const uint16_t *q, long long n, float lo, float hi, float *x, void *stream);
 
+/* ---- dense track store: every frame's (template -> frame) result kept on the device in the ".flowouX16" quantisation above,
+ * one 8-byte word per pixel, and read out at any points afterwards (mft_amd/trackstore.py: DenseTrackStore).
+ *
+ * A stored frame is
+ *   packed [H][W][4] uint16 (8-byte aligned): (flow x, flow y, occlusion, sigma) of the pixel, and
+ *   lohi   [4][2] float32: (min, max) of flow x, flow y, occlusion, sigma -- each channel on its own, as write_flowou_X16
+ *          compresses them (MFT/utils/io.py:495-533).
+ * Both are device memory of the caller.  Plane pointers (flow [2][H][W], occl / sigma [1][H][W]) need 4-byte alignment only:
+ * planes sliced out of a larger buffer are taken as they are.  H, W >= 2.
+ *
+ * mftx_trackstore_append: planes -> packed, lohi.  Two launches: per-block partial (min, max) of all four channels in one
+ * pass over the planes; then every block re-reduces the partials and quantises + packs its pixels.  Every channel's q and
+ * (lo, hi) are bitwise what mftx_quantize_u16 gives for that plane alone, the flat branch (|hi - lo| < 1e-8 -> q = 0)
+ * included.  workspace: mftx_trackstore_workspace_bytes() bytes of device memory (the partials). */
+size_t mftx_trackstore_workspace_bytes(void);
+int mftx_trackstore_append(const float *flow, const float *occl, const float *sigma, int H, int W,
+                           uint16_t *packed, float *lohi, void *workspace, size_t workspace_bytes, void *stream);
+
+/* One stored frame back to planes: per channel bitwise mftx_dequantize_u16 with that channel's (lo, hi), which are read
+ * from device memory here (no host round trip).  For forward warps / overlays after the fact, and for export. */
+int mftx_trackstore_unpack(const uint16_t *packed, const float *lohi, int H, int W,
+                           float *flow, float *occl, float *sigma, void *stream);
+
+/* N points over T stored frames in one call.  The store is a list of chunks: chunks / lohi_chunks are HOST arrays of
+ * n_chunks device pointers, chunk c holding frames_per_chunk frames -- [frames_per_chunk][H][W][4] uint16 with
+ * [frames_per_chunk][4][2] float32 beside it -- so that slot s is frame s % frames_per_chunk of chunk s / frames_per_chunk.
+ * slots [T] int32 (device): the slots to read, in the order of the table's columns; xy [N][2] float32 (device).
+ * For point i and the j-th requested slot the frame's four channels are sampled at xy[i] exactly as mftx_sample_points
+ * samples planes (bilinear, zeros outside, align_corners=True, the normalise / un-normalise round trip, the same taps in
+ * the same order), every in-frame tap dequantised first as mftx_dequantize_u16 does it -- ((float)q / 65535) * (hi - lo) + lo;
+ * an out-of-frame tap is 0 -- and (x + flow x, y + flow y, occlusion, sigma) is written as one 16-byte store to
+ * table[i * row_stride + 4 * (column0 + j)] (device, float32, 16-byte aligned; row_stride in floats, a multiple of 4 with
+ * row_stride >= 4 * (column0 + T)).  Bitwise mftx_sample_points on the frames' mftx_trackstore_unpack'ed planes.
+ * Every other word of the table is left alone, and so are the columns of slots outside 0 .. n_chunks * frames_per_chunk - 1.
+ * The chunk descriptors travel in the kernel arguments: one launch per 192 chunks, no allocation, no copy, no
+ * synchronisation.  T == 0 or N == 0: nothing is done, 0 is returned. */
+int mftx_trackstore_query(const uint16_t *const *chunks, const float *const *lohi_chunks, int n_chunks, int frames_per_chunk,
+                          const int *slots, int T, int H, int W, int N, const float *xy,
+                          float *table, long long row_stride, int column0, void *stream);
+
 /* ---- 8f-4: frame / result transport without copy queues -------------------------------------------------------------------
  * A copy KERNEL: src -> dst, n bytes, both 16-byte aligned; either may be PINNED HOST memory (hipHostMalloc / torch
  * pin_memory: mapped into the device's address space), which a kernel reads and writes over PCIe directly.  Unlike

@@ -86,6 +86,8 @@ class MFT():
         assert time_direction in [+1, -1]
         self.time_direction = time_direction
         self.flow_cache = flow_cache
+        if self.C.track_store and self.C.delta_sharding:
+            raise ValueError("C.track_store does not support C.delta_sharding (multi-GPU): the frames' results are spread over the ranks")
         self._reset_guard_state()
         if hasattr(self.flower, "reset_cache"):
             self.flower.reset_cache()
@@ -103,12 +105,30 @@ class MFT():
         self.last_pairs = []
         self.last_chosen = None
         self._window_ids = set()
+        self.track_store = self._new_track_store()
+        if self.track_store is not None:
+            self.track_store.append(self.memory[self.start_frame_i]['result'], self.start_frame_i)
         if self.C.delta_sharding:
             from .dist import WindowSharder
             self.sharder = WindowSharder.from_environment()
         meta = SimpleNamespace()
         meta.result = self.memory[self.start_frame_i]['result'].clone().cpu()
         return meta
+
+    def _new_track_store(self):
+        """C.track_store (off unless set): a fresh ``DenseTrackStore`` that keeps every frame's selected result in 16 bits on the
+        tracker's device (mft_amd/trackstore.py), for point read-outs after the pass.  C.track_store_max_bytes bounds it
+        (``MemoryError`` from the ``track()`` that would exceed it), C.track_store_frames_per_chunk sets how it grows."""
+        if not self.C.track_store:
+            return None
+        from .trackstore import DenseTrackStore
+        kw = {}
+        if self.C.track_store_frames_per_chunk:
+            kw["frames_per_chunk"] = int(self.C.track_store_frames_per_chunk)
+        max_bytes = self.C.track_store_max_bytes
+        if isinstance(max_bytes, (int, float)) and not isinstance(max_bytes, bool):
+            kw["max_bytes"] = int(max_bytes)
+        return DenseTrackStore(self.img_H, self.img_W, device=self.device, **kw)
 
     def _reset_guard_state(self):
         """init() on a used tracker starts clean: nothing of the previous sequence's non-finite guard may raise in the new one.  The
@@ -198,6 +218,8 @@ class MFT():
             logger.debug("chain + selection (%d candidates, one kernel): %.2fms", len(lefts), t0.elapsed_time(t1))
         # invalid flows are already marked occluded inside the selection kernel
         result = FlowOUTrackingResult(flow, occl, sigma, validate=False)
+        if getattr(self, "track_store", None) is not None:         # two kernels on this stream, before anything goes to the host
+            self.track_store.append(result, frame_i)
         lazy = self._lazy_host_results() and flow.is_cuda and not self.C.keep_result_on_device
         if self.C.keep_result_on_device:
             meta.result = result.clone()       # a copy: the consumer may move it in place (meta.result.cpu())

@@ -124,6 +124,8 @@ class MultiTemplateMFT(MFT):
         assert time_direction in [+1, -1]
         if flow_cache is not None:
             raise ValueError("MultiTemplateMFT takes no flow cache: within one pass no pair is requested twice")
+        if self.C.track_store:
+            raise ValueError("MultiTemplateMFT takes no C.track_store: its queries are read out during the pass (point_tracks)")
         if self.C.delta_sharding:
             raise ValueError("MultiTemplateMFT does not support C.delta_sharding (multi-GPU): run one pass per GPU instead")
         starts = sorted({int(s) for s in start_frames}, reverse=time_direction < 0)

@@ -944,6 +944,79 @@ def dequantize_u16(q, lo, hi):
     return x
 
 
+# ---------------------------------------------------------------------------
+# dense track store (csrc/trackstore.hip): frames kept as 8 bytes per pixel, point read-out from the quantised data
+# ---------------------------------------------------------------------------
+
+_trackstore_ws = {}
+
+
+def _trackstore_frame(packed, lohi, H, W):
+    if tuple(packed.shape) != (H, W, 4) or tuple(lohi.shape) != (4, 2):
+        raise MftxError("trackstore: packed must be [H,W,4] uint16 and lohi [4,2] float32")
+    return _chk(packed, "packed", torch.uint16), _chk(lohi, "lohi")
+
+
+def trackstore_append(planes, packed, lohi):
+    """One result (flow[2,H,W], occl[1,H,W], sigma[1,H,W]) -> ``packed`` [H,W,4] uint16 = (fx, fy, occl, sigma) per pixel and
+    ``lohi`` [4,2] float32 = each channel's (min, max), both the caller's device tensors (``mftx_trackstore_append``).  Per
+    channel bitwise ``quantize_u16`` of that plane; the planes may be views into a larger buffer.  No host sync."""
+    lib = _lib.load()
+    _, H, W = planes[0].shape
+    H, W = int(H), int(W)
+    fp, op, sp = _planes(planes, H, W)
+    pp, lp = _trackstore_frame(packed, lohi, H, W)
+    dev = packed.device
+    ws = _trackstore_ws.get(dev)
+    if ws is None:
+        ws = _trackstore_ws[dev] = torch.empty(lib.mftx_trackstore_workspace_bytes(), dtype=torch.uint8, device=dev)
+    check(lib.mftx_trackstore_append(fp, op, sp, H, W, pp, lp, ws.data_ptr(), ws.numel(), _stream()), "mftx_trackstore_append")
+    return packed, lohi
+
+
+def trackstore_unpack(packed, lohi, out=None):
+    """One stored frame -> (flow[2,H,W], occl[1,H,W], sigma[1,H,W]) on the device (``mftx_trackstore_unpack``): per channel
+    bitwise ``dequantize_u16`` with the (min, max) of ``lohi``, which stay on the device.  ``out``: planes to write into."""
+    lib = _lib.load()
+    H, W = int(packed.shape[0]), int(packed.shape[1])
+    pp, lp = _trackstore_frame(packed, lohi, H, W)
+    if out is None:
+        out = _new_result(H, W, packed.device)
+    fp, op, sp = _planes(out, H, W)
+    check(lib.mftx_trackstore_unpack(pp, lp, H, W, fp, op, sp, _stream()), "mftx_trackstore_unpack")
+    return out
+
+
+def trackstore_query(chunks, lohi_chunks, slots, xy, table, column0=0):
+    """Point read-out of stored frames in one call (``mftx_trackstore_query``).  chunks: uint16 device tensors
+    [frames_per_chunk, H, W, 4] with lohi_chunks float32 [frames_per_chunk, 4, 2] beside them (slot s = frame
+    s % frames_per_chunk of chunk s // frames_per_chunk); slots [T] int32 and xy [N,2] float32 on the device; table: a float32
+    device tensor [N, frames, 4] the caller owns.  Row i, column ``column0 + j`` receives (x + flow x, y + flow y, occlusion,
+    sigma) of point i on the frame in slots[j] -- bitwise ``sample_points`` on that frame's ``trackstore_unpack``-ed planes;
+    nothing else of the table is touched.  Returns ``table``."""
+    lib = _lib.load()
+    chunks, lohi_chunks = list(chunks), list(lohi_chunks)
+    if not chunks or len(chunks) != len(lohi_chunks):
+        raise MftxError("trackstore_query: as many lohi tables as chunks, at least one")
+    fpc, H, W = (int(s) for s in chunks[0].shape[:3])
+    for c, l in zip(chunks, lohi_chunks):
+        if tuple(c.shape) != (fpc, H, W, 4) or tuple(l.shape) != (fpc, 4, 2):
+            raise MftxError("trackstore_query: chunks must be [frames_per_chunk,H,W,4] with lohi [frames_per_chunk,4,2]")
+    if xy.dim() != 2 or int(xy.shape[1]) != 2 or slots.dim() != 1:
+        raise MftxError("trackstore_query: slots must be [T], xy [N, 2]")
+    N, T = int(xy.shape[0]), int(slots.shape[0])
+    if table.dim() != 3 or int(table.shape[0]) != N or int(table.shape[2]) != 4:
+        raise MftxError("trackstore_query: the table must be [N, frames, 4]")
+    carr = _lib.ptr_array([_chk(c, "chunk", torch.uint16) for c in chunks])
+    larr = _lib.ptr_array([_chk(l, "lohi chunk") for l in lohi_chunks])
+    if N == 0 or T == 0:          # (empty tensors have no storage to point at)
+        return table
+    check(lib.mftx_trackstore_query(carr[0], larr[0], len(chunks), fpc, _chk(slots, "slots", torch.int32), T, H, W, N,
+                                    _chk(xy, "xy"), _chk(table, "table"), 4 * int(table.shape[1]), int(column0), _stream()),
+          "mftx_trackstore_query")
+    return table
+
+
 class RaftEngine:
     """Handle on the native refinement runtime (``mftx_raft_*``)."""
 

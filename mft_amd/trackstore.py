@@ -1,0 +1,194 @@
+"""DenseTrackStore -- every frame's dense (template -> frame) result kept in 16 bits, any point's track read out afterwards.
+
+MFT tracks every pixel, but the tracker keeps only the frames its deltas still need (``MFT.cleanup_memory``), and the point
+read-outs that exist (``mftx_sample_points``) want the queries before the video is tracked.  This store keeps what the tracker
+computed: each appended result is quantised the way the reference's flow cache quantises its entries (``.flowouX16``: per-channel
+min / max, uint16, round-half-even -- MFT/utils/io.py:495-512, read back by :548-551) into ONE 8-byte word per pixel
+(fx, fy, occlusion, sigma), 8 B/px instead of 16 B/px, and ``query`` answers "these N points over these T frames" in one
+kernel call straight from the quantised frames (csrc/trackstore.hip).  The precision is what the reference accepts for every
+flow that passes through its disk cache: half a quantisation step of each channel's range.
+
+    store = DenseTrackStore(H, W)                     # or: config.track_store = True -> tracker.track_store
+    store.append(result, frame_i)                     # on the current stream, no host wait
+    table = store.query(points)                       # device [N, T, 4]: x, y, occlusion, sigma per frame, append order
+    coords, occl = store.tracks(points, frames=[...]) # numpy, the shape MultiTemplateMFT.point_tracks() gives
+    result = store.result(frame_i)                    # the dequantised FlowOUTrackingResult, on the device
+
+``device="cpu"`` is a host restatement of the same operations (numpy / torch), which pins the semantics without a GPU.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .results import FlowOUTrackingResult
+
+U16_MAX = 2 ** 16 - 1
+
+
+def compress_channel(xs):
+    """One channel -> (uint16 array, min, max): the quantisation of a ``.flowouX16`` entry, in float32 as numpy evaluates it
+    (a channel whose range is below 1e-8 becomes all zeros)."""
+    x = np.asarray(xs, dtype=np.float32)
+    lo, hi = x.min(), x.max()
+    if np.abs(hi - lo) < 1e-8:
+        unit = np.zeros_like(x)
+    else:
+        unit = (x - lo) / (hi - lo)
+    return np.round(unit * U16_MAX).astype(np.uint16), lo, hi
+
+
+def decompress_channel(q, lo, hi):
+    """The inverse: uint16 array + the channel's (min, max) -> float32."""
+    lo, hi = np.float32(lo), np.float32(hi)
+    return (np.asarray(q).astype(np.float32) / U16_MAX) * (hi - lo) + lo
+
+
+class DenseTrackStore:
+    def __init__(self, H, W, device="cuda", frames_per_chunk=64, max_bytes=None):
+        """A store of H x W frames.  Storage grows by chunks of ``frames_per_chunk`` frames (torch allocations on ``device``);
+        ``max_bytes`` (optional) bounds ``nbytes``: the append that would exceed it raises ``MemoryError`` instead."""
+        self.H, self.W = int(H), int(W)
+        if self.H < 2 or self.W < 2:
+            raise ValueError("DenseTrackStore: H and W must be >= 2")
+        self.device = torch.device(device)
+        self.frames_per_chunk = int(frames_per_chunk)
+        if self.frames_per_chunk < 1:
+            raise ValueError("DenseTrackStore: frames_per_chunk must be at least 1")
+        self.max_bytes = None if max_bytes is None else int(max_bytes)
+        self.frame_ids = []          # in append order: frame_ids[slot] is the frame held by that slot
+        self._slot_of = {}
+        self._chunks = []            # uint16 [frames_per_chunk, H, W, 4]
+        self._lohi = []              # float32 [frames_per_chunk, 4, 2]
+
+    # ------------------------------------------------------------------ bookkeeping
+    @property
+    def native(self):
+        return self.device.type != "cpu"
+
+    @property
+    def chunk_bytes(self):
+        return self.frames_per_chunk * (self.H * self.W * 8 + 4 * 2 * 4)
+
+    @property
+    def nbytes(self):
+        """Bytes of storage held: whole chunks, packed frames plus their (min, max) tables."""
+        return len(self._chunks) * self.chunk_bytes
+
+    def __len__(self):
+        return len(self.frame_ids)
+
+    def slot_of(self, frame_i):
+        """The slot that holds frame ``frame_i`` (``KeyError`` if it was never appended)."""
+        return self._slot_of[int(frame_i)]
+
+    def packed(self, slot):
+        """View [H, W, 4] uint16 of the slot's quantised frame."""
+        slot = self._check_slot(slot)
+        return self._chunks[slot // self.frames_per_chunk][slot % self.frames_per_chunk]
+
+    def lohi(self, slot):
+        """View [4, 2] float32: (min, max) of flow x, flow y, occlusion, sigma of the slot's frame."""
+        slot = self._check_slot(slot)
+        return self._lohi[slot // self.frames_per_chunk][slot % self.frames_per_chunk]
+
+    def _check_slot(self, slot):
+        slot = int(slot)
+        if not 0 <= slot < len(self.frame_ids):
+            raise IndexError(f"DenseTrackStore: no slot {slot} ({len(self.frame_ids)} frames stored)")
+        return slot
+
+    def _grow(self):
+        if self.max_bytes is not None and self.nbytes + self.chunk_bytes > self.max_bytes:
+            raise MemoryError(f"DenseTrackStore: another chunk of {self.frames_per_chunk} frames ({self.chunk_bytes} bytes) would "
+                              f"exceed max_bytes = {self.max_bytes} ({self.nbytes} bytes held)")
+        self._chunks.append(torch.empty((self.frames_per_chunk, self.H, self.W, 4), dtype=torch.uint16, device=self.device))
+        self._lohi.append(torch.zeros((self.frames_per_chunk, 4, 2), dtype=torch.float32, device=self.device))
+
+    # ------------------------------------------------------------------ append
+    def append(self, result_or_planes, frame_i=None):
+        """Store one result -- a ``FlowOUTrackingResult`` or its (flow[2,H,W], occl[1,H,W], sigma[1,H,W]) planes -- as frame
+        ``frame_i`` (default: the number of frames stored so far) and return its slot.  Frames may come in any order, each id
+        once (``ValueError``).  On the device this enqueues two kernels on the current stream and never waits for the GPU."""
+        planes = result_or_planes.planes() if hasattr(result_or_planes, "planes") else tuple(result_or_planes)
+        frame_i = len(self.frame_ids) if frame_i is None else int(frame_i)
+        if frame_i in self._slot_of:
+            raise ValueError(f"DenseTrackStore: frame {frame_i} is stored already (slot {self._slot_of[frame_i]})")
+        flow, occl, sigma = planes
+        if tuple(flow.shape) != (2, self.H, self.W) or tuple(occl.shape) != (1, self.H, self.W) or \
+                tuple(sigma.shape) != (1, self.H, self.W):
+            raise ValueError(f"DenseTrackStore: planes must be [2,H,W], [1,H,W], [1,H,W] with H x W = {self.H} x {self.W}")
+        slot = len(self.frame_ids)
+        if slot == len(self._chunks) * self.frames_per_chunk:
+            self._grow()
+        chunk, k = slot // self.frames_per_chunk, slot % self.frames_per_chunk
+        if self.native:
+            from . import ops
+            planes = tuple(torch.as_tensor(p).to(device=self.device, dtype=torch.float32).contiguous() for p in planes)
+            ops.trackstore_append(planes, self._chunks[chunk][k], self._lohi[chunk][k])
+        else:
+            pk, lh = self._chunks[chunk].numpy(), self._lohi[chunk].numpy()
+            src = [torch.as_tensor(p).detach().cpu().numpy() for p in planes]
+            for c, x in enumerate((src[0][0], src[0][1], src[1][0], src[2][0])):
+                q, lo, hi = compress_channel(x)
+                pk[k, :, :, c] = q
+                lh[k, c] = (lo, hi)
+        self.frame_ids.append(frame_i)
+        self._slot_of[frame_i] = slot
+        return slot
+
+    # ------------------------------------------------------------------ read-out
+    def _slots(self, frames):
+        if frames is None:
+            return list(range(len(self.frame_ids)))
+        return [self.slot_of(f) for f in frames]           # KeyError for a frame that was never appended
+
+    def query(self, points, frames=None, out=None):
+        """points (N, 2) xy on the template frame; frames: a sequence of frame ids (default: all, in append order) ->
+        float32 tensor [N, T, 4] on the store's device: (x, y, occlusion, sigma) of every point in every requested frame --
+        ``warp_forward_points`` and ``sample`` of the results API on the dequantised frames.  ``out``: a [N, T, 4] tensor to
+        write into.  On the device: one kernel call, and with ``points`` a device tensor no host synchronisation."""
+        slots = self._slots(frames)
+        if not isinstance(points, torch.Tensor):
+            points = torch.from_numpy(np.ascontiguousarray(np.asarray(points, dtype=np.float32)))
+        xy = points.to(device=self.device, dtype=torch.float32).reshape(-1, 2).contiguous()
+        N, T = int(xy.shape[0]), len(slots)
+        if out is None:
+            out = torch.zeros((N, T, 4), dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != (N, T, 4) or out.dtype != torch.float32 or out.device != xy.device:
+            raise ValueError(f"DenseTrackStore.query: out must be a float32 [{N}, {T}, 4] tensor on {self.device}")
+        if N == 0 or T == 0:
+            return out
+        if self.native:
+            from . import ops
+            if frames is None:
+                st = torch.arange(T, dtype=torch.int32, device=self.device)
+            else:
+                st = torch.tensor(slots, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
+            ops.trackstore_query(self._chunks, self._lohi, st, xy, out, 0)
+        else:
+            for j, slot in enumerate(slots):
+                r = self._result_of_slot(slot)
+                out[:, j, 0:2] = r.warp_forward_points(xy)
+                _, o, s = r.sample(xy)
+                out[:, j, 2], out[:, j, 3] = o[0], s[0]
+        return out
+
+    def tracks(self, points, frames=None):
+        """-> numpy (coords [N, T, 2], occlusion [N, T]), the shape ``MultiTemplateMFT.point_tracks()`` gives.  ONE download;
+        it synchronises."""
+        table = self.query(points, frames).cpu().numpy()
+        return table[:, :, 0:2].copy(), table[:, :, 2].copy()
+
+    def _result_of_slot(self, slot):
+        if self.native:
+            from . import ops
+            return FlowOUTrackingResult(*ops.trackstore_unpack(self.packed(slot), self.lohi(slot)), validate=False)
+        pk, lh = self.packed(slot).numpy(), self.lohi(slot).numpy()
+        ch = [torch.from_numpy(np.ascontiguousarray(decompress_channel(pk[:, :, c], lh[c, 0], lh[c, 1]))) for c in range(4)]
+        return FlowOUTrackingResult(torch.stack(ch[0:2]), ch[2][None], ch[3][None], validate=False)
+
+    def result(self, frame_i):
+        """The stored frame, dequantised: a ``FlowOUTrackingResult`` on the store's device (for ``draw_edit`` /
+        ``warp_forward_device`` after the fact, and for export)."""
+        return self._result_of_slot(self.slot_of(frame_i))

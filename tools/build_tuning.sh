@@ -13,6 +13,7 @@ for f in corr corr_ondemand upsample encoder raft_engine; do jobs+=("$f.hip|$f.o
 for k in 0 1 2 3; do jobs+=("conv_gemm.hip|conv_gemm_p$k.o|-DMFTX_CONV_PART=$k"); done
 jobs+=("chain.hip|chain.o|-ffp-contract=off -fno-slp-vectorize $NOPK" "codec.hip|codec.o|-ffp-contract=off $NOPK" "api.cpp|api.o|-x hip")
 jobs+=("splat.hip|splat.o|-ffp-contract=off -fno-slp-vectorize $NOPK")
+jobs+=("trackstore.hip|trackstore.o|-ffp-contract=off -fno-slp-vectorize $NOPK")
 printf '%s\n' "${jobs[@]}" | xargs -P 8 -I{} bash -c 'IFS="|" read s o x <<< "{}"; /opt/rocm/bin/hipcc '"$FLAGS"' $x -c '"$SRC"'/$s -o '"$OBJ"'/$o'
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build_tune/libmftx_tune.so $OBJ/*.o
 ls -la build_tune/libmftx_tune.so
