@@ -2,7 +2,7 @@
 """Track every pixel of a video with MFT and write the point / edit overlays -- the reference's ``demo.py`` on
 the MI355X engine.
 
-    python demo.py --video <dir of PNG frames | frames.npy> [--edit edit.png] [--out demo_out/] [--synthetic] [--gpu-overlays | --track-store]
+    python demo.py --video <dir of PNG frames | frames.npy> [--edit edit.png] [--out demo_out/] [--synthetic] [--gpu-overlays | --track-store [--query-frame Q]]
 
 Differences forced by the environment: no OpenCV here, so the input is a directory of PNG frames or a ``.npy``
 frame array (video containers work when cv2 is importable) and the overlays are written as numbered PNGs instead of
@@ -11,7 +11,9 @@ this build).  Frames go to the GPU through a pinned upload ring (``mft_amd/video
 both overlays are rendered on the GPU inside the tracking loop (``mft_amd/vis.py:DeviceOverlay``) and written as they
 arrive: no dense result is downloaded or kept.  With ``--track-store`` the tracker keeps every frame's dense result on the GPU in
 16 bits (``mft_amd/trackstore.py``: 8 bytes per pixel) and nothing is downloaded inside the loop; afterwards ONE read-out gives the
-points of all frames, and the edit overlay is drawn from the stored frames.
+points of all frames, and the edit overlay is drawn from the stored frames.  ``--query-frame Q`` takes the query grid on frame Q
+instead of frame 0: the stored map of frame Q is inverted at the grid (``DenseTrackStore.tracks_from``), and grid points that no
+template point maps to are drawn as occluded.
 """
 import argparse
 import logging
@@ -44,6 +46,7 @@ def parse_arguments():
     ap.add_argument('--synthetic_weights_seed', type=int, default=None, help='run on seeded stand-in weights')
     ap.add_argument('--gpu-overlays', action='store_true', help='render the overlays on the GPU while tracking; dense results stay on the device')
     ap.add_argument('--track-store', action='store_true', help='keep every dense result on the GPU in 16 bits; read the points out after the pass')
+    ap.add_argument('--query-frame', type=int, default=None, metavar='Q', help='with --track-store: take the query grid on frame Q instead of frame 0')
     return ap.parse_args()
 
 
@@ -59,6 +62,8 @@ def run(args):
         if args.gpu_overlays:
             raise SystemExit("--track-store and --gpu-overlays are two ways to avoid the per-frame download: choose one")
         config.track_store = True
+    elif args.query_frame is not None:
+        raise SystemExit("--query-frame reads the track store: give --track-store too")
     tracker = config.tracker_class(config)
     if args.synthetic:
         from mft_amd.synth import SyntheticVideo
@@ -116,7 +121,11 @@ def run_track_store(args, tracker, frames, name):
     store = tracker.track_store
     logger.info("track store: %d frames, %.1f MB on the device", len(store), store.nbytes / 1e6)
     queries = vis.get_queries(frames[0].shape[:2], args.grid_spacing)
-    coords, occlusions = store.tracks(queries, frames=range(len(frames)))
+    if args.query_frame is None:
+        coords, occlusions = store.tracks(queries, frames=range(len(frames)))
+    else:
+        coords, occlusions, found = store.tracks_from(queries, args.query_frame, frames=range(len(frames)))
+        logger.info("query grid on frame %d: %d of %d points are images of template points", args.query_frame, int(found.sum()), len(found))
     edit = vio.imread_unchanged(args.edit) if args.edit.exists() else None
     for i, frame in enumerate(frames):
         vio.imwrite_bgr(args.out / f"{name}_points" / f"{i:05d}.png", vis.draw_dots(frame, coords[:, i], occlusions[:, i]))

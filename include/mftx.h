@@ -626,6 +626,26 @@ int mftx_trackstore_query(const uint16_t *const *chunks, const float *const *loh
                           const int *slots, int T, int H, int W, int N, const float *xy,
                           float *table, long long row_stride, int column0, void *stream);
 
+/* The stored map inverted: N points given ON stored frames -> the template points they are the images of.
+ * The N queries come in G groups of one frame each.  All tables are DEVICE memory:
+ *   frames [G]: the groups' packed frames ([H][W][4] uint16 each), lohis [G]: their [4][2] float32 tables;
+ *   group_start [G + 1], order [N]: group g is the queries order[group_start[g] .. group_start[g + 1] - 1] (indices into xy,
+ *   a permutation of 0 .. N - 1); group_of [N]: the group of query n; xy [N][2] float32, in the caller's order.
+ * Template cell c = i * (W - 1) + j is mapped by the bilinear patch of its four corner images (j + flow x, i + flow y),
+ * dequantised as above.  A cell whose corner images' bounding box, widened by eps = 2^-10 px, holds the query is solved by 6
+ * Newton steps from (u, v) = (0.5, 0.5) in float32 (+ - * / only, in the order of csrc/trackstore.hip ts_solve_cell), (u, v)
+ * clamped into [0, 1]; it is a candidate iff (u, v) were finite and the patch at the clamped (u, v) is within eps of the
+ * query in x and in y.  Among the candidates the smallest key wins: bit 63 = occlusion > occlusion_threshold, bits 62..32
+ * = the bits of sigma (not > 0: +0), bits 31..0 = c, occlusion and sigma interpolated at (u, v) from the cell's corners.
+ *   keys [N] 64-bit words (8-byte aligned): workspace, set to all ones by this call, then one 64-bit integer atomic minimum
+ *   per wave and query -- the result does not depend on any order;
+ *   table [N][4] float32 (16-byte aligned): template x = j + u, template y = i + v, occlusion, sigma of query n; cell [N] int32.
+ * A query without a candidate gets cell = -1 and four NaNs (0x7fc00000).  One memset and two launches whatever G is; no
+ * allocation, no synchronisation.  N == 0: nothing is done, 0 is returned. */
+int mftx_trackstore_locate(const uint16_t *const *frames, const float *const *lohis, const int *group_start, int G,
+                           const int *order, const int *group_of, int H, int W, int N, const float *xy,
+                           float occlusion_threshold, unsigned long long *keys, float *table, int *cell, void *stream);
+
 /* ---- 8f-4: frame / result transport without copy queues -------------------------------------------------------------------
  * A copy KERNEL: src -> dst, n bytes, both 16-byte aligned; either may be PINNED HOST memory (hipHostMalloc / torch
  * pin_memory: mapped into the device's address space), which a kernel reads and writes over PCIe directly.  Unlike

@@ -8,6 +8,9 @@
 //   unpack : packed + lohi -> planes, per channel bitwise mftx_dequantize_u16 (lo, hi read from device memory).
 //   query  : chain.hip's sample_points_kernel, its taps dequantised with dequantize_kernel's dec() -- an out-of-frame tap is 0,
 //            not dec(0) = lo.  Bitwise mftx_sample_points on the unpacked planes.
+//   locate : the inverse -- points given ON stored frames -> the template points they are the images of: a search over the
+//            template's cells (bilinear patches solved by Newton steps, the winner a 64-bit integer atomic minimum) and a resolve
+//            kernel.  Bitwise the numpy float32 restatement in mft_amd/trackstore.py.
 //
 // Planes are read and written one float per lane (four pixels per thread in flight): their bases need 4-byte alignment only
 // (flow y of a [2][H][W] tensor and the planes of a [4][H][W] buffer sit H * W floats apart, which is no multiple of 16
@@ -218,6 +221,166 @@ __global__ __launch_bounds__(256) void ts_query_kernel(ChunkSet cs, int c0, int 
     }
 }
 
+// ---- locate: the stored map inverted at points given ON a stored frame ------------------------------------------------------------
+// Template cell (i, j) .. (i + 1, j + 1) is mapped by the bilinear patch F(u, v) = A + u e + v g + u v h of its corner images
+// A = M(i, j), B = M(i, j + 1), C = M(i + 1, j), D = M(i + 1, j + 1), M(i, j) = (j + fx, i + fy) dequantised.  A cell can hold
+// the query Q only if Q is in the corners' bounding box widened by TL_EPS; there TL_NEWTON Newton steps on F - Q = 0 from the
+// cell's centre, (u, v) clamped into [0, 1], and the cell is a candidate iff (u, v) were finite and |F - Q| <= TL_EPS in both
+// coordinates at the clamped (u, v).  The winner is the smallest key (occluded, sigma, cell) as ONE 64-bit integer -- bit 63
+// occlusion > threshold, bits 62..32 the bits of sigma (a sigma that is not > 0 counts as +0), bits 31..0 the cell -- so the
+// minimum does not depend on the order it is taken in.  mft_amd/trackstore.py (_solve_cells, _locate_host) is the same
+// arithmetic in numpy float32, operation by operation: + - * / only, no contraction (this file's flags).
+constexpr float TL_EPS = 0.0009765625f;        // 2^-10 px
+constexpr int TL_NEWTON = 6;
+constexpr int TL_TW = 32, TL_TH = 8;           // cells per workgroup: one per lane, a wave owns two rows of 32
+constexpr unsigned long long TL_NONE = ~0ull;
+
+struct LocCell { float ax, ay, bx, by, cx, cy, dx, dy; };
+
+__device__ __forceinline__ float ts_clamp01(float t) { return t < 0.f ? 0.f : (t > 1.f ? 1.f : t); }
+
+// -> candidate?  (u, v) are the clamped solution either way.
+__device__ __forceinline__ bool ts_solve_cell(const LocCell &c, float qx, float qy, float &u, float &v) {
+    const float ex = c.bx - c.ax, ey = c.by - c.ay, gx = c.cx - c.ax, gy = c.cy - c.ay;
+    const float hx = ((c.ax - c.bx) - c.cx) + c.dx, hy = ((c.ay - c.by) - c.cy) + c.dy;
+    u = 0.5f; v = 0.5f;
+#pragma unroll 1
+    for (int it = 0; it < TL_NEWTON; ++it) {
+        const float uv = u * v;
+        const float rx = (((c.ax + u * ex) + v * gx) + uv * hx) - qx;
+        const float ry = (((c.ay + u * ey) + v * gy) + uv * hy) - qy;
+        const float j00 = ex + v * hx, j01 = gx + u * hx, j10 = ey + v * hy, j11 = gy + u * hy;
+        const float det = j00 * j11 - j01 * j10;
+        const float du = (rx * j11 - ry * j01) / det, dv = (ry * j00 - rx * j10) / det;
+        u = u - du;
+        v = v - dv;
+    }
+    const bool finite = fabsf(u) <= FLT_MAX && fabsf(v) <= FLT_MAX;
+    u = ts_clamp01(u); v = ts_clamp01(v);          // (a NaN stays one; `finite` has refused it already)
+    const float uv = u * v;
+    const float rx = (((c.ax + u * ex) + v * gx) + uv * hx) - qx;
+    const float ry = (((c.ay + u * ey) + v * gy) + uv * hy) - qy;
+    return finite && fabsf(rx) <= TL_EPS && fabsf(ry) <= TL_EPS;
+}
+
+// the sampler's four weights and its order of summation
+__device__ __forceinline__ float ts_mix(float a, float b, float c, float d, float u, float v) {
+    const float w00 = (1.f - u) * (1.f - v), w01 = u * (1.f - v), w10 = (1.f - u) * v, w11 = u * v;
+    return a * w00 + b * w01 + c * w10 + d * w11;
+}
+
+__device__ __forceinline__ unsigned long long ts_locate_key(float occl, float sigma, float thr, unsigned cell) {
+    const float s = sigma > 0.f ? sigma : 0.f;
+    return ((unsigned long long)(occl > thr ? 1u : 0u) << 63) | ((unsigned long long)(__float_as_uint(s) & 0x7fffffffu) << 32) | cell;
+}
+
+// Grid: cell tiles x frame groups (blockIdx.x = group * tiles + tile).  A group is the run order[group_start[g] ..
+// group_start[g + 1]) of queries given on one frame.  Each wave tests 64 queries at a time against the box of its 64 cells, a
+// query per lane; only the queries that pass are walked one by one, each lane with its own cell.
+__global__ __launch_bounds__(256) void ts_locate_search_kernel(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
+                                                               const int *__restrict__ group_start, const int *__restrict__ order,
+                                                               int tiles_x, int tiles, int H, int W, const float *__restrict__ xy,
+                                                               float thr, unsigned long long *__restrict__ keys) {
+    __shared__ float4 corner[TL_TH + 1][TL_TW + 1];       // (M x, M y, occlusion, sigma) of the tile's corners
+    const int g = blockIdx.x / tiles, tile = blockIdx.x % tiles;
+    const int i0 = (tile / tiles_x) * TL_TH, j0 = (tile % tiles_x) * TL_TW;
+    const uint2 *__restrict__ frame = frames[g];
+    const int lane = threadIdx.x & 63;
+    // the wave's first 64 queries are fetched while the tile is staged (a group of few queries is one pass of the loop below)
+    int k0 = group_start[g];
+    const int k_end = group_start[g + 1];
+    int p = k0 + lane < k_end ? order[k0 + lane] : -1;
+    float px = 0.f, py = 0.f;
+    if (p >= 0) { px = xy[2 * (long long)p]; py = xy[2 * (long long)p + 1]; }
+    const Dec4 dec(lohis[g]);
+    for (int e = threadIdx.x; e < (TL_TH + 1) * (TL_TW + 1); e += 256) {
+        const int ci = e / (TL_TW + 1), cj = e % (TL_TW + 1);
+        const int i = min(i0 + ci, H - 1), j = min(j0 + cj, W - 1);           // (a ragged tile's cells beyond the frame are never used)
+        const float4 t = dec(frame[(long long)i * W + j]);
+        corner[ci][cj] = make_float4((float)j + t.x, (float)i + t.y, t.z, t.w);
+    }
+    __syncthreads();
+    const int li = threadIdx.x / TL_TW, lj = threadIdx.x % TL_TW;
+    const bool active = i0 + li < H - 1 && j0 + lj < W - 1;
+    const unsigned cell = (unsigned)((i0 + li) * (W - 1) + (j0 + lj));
+    const float4 ta = corner[li][lj], tb = corner[li][lj + 1], tc = corner[li + 1][lj], td = corner[li + 1][lj + 1];
+    const LocCell c = {ta.x, ta.y, tb.x, tb.y, tc.x, tc.y, td.x, td.y};
+    // the cell's widened box: empty for a lane without a cell
+    float lox = FLT_MAX, hix = -FLT_MAX, loy = FLT_MAX, hiy = -FLT_MAX;
+    if (active) {
+        lox = fminf(fminf(c.ax, c.bx), fminf(c.cx, c.dx)) - TL_EPS;
+        hix = fmaxf(fmaxf(c.ax, c.bx), fmaxf(c.cx, c.dx)) + TL_EPS;
+        loy = fminf(fminf(c.ay, c.by), fminf(c.cy, c.dy)) - TL_EPS;
+        hiy = fmaxf(fmaxf(c.ay, c.by), fmaxf(c.cy, c.dy)) + TL_EPS;
+    }
+    // ... and the union over the wave's cells: a query outside it is in no lane's box
+    float wlox = lox, whix = hix, wloy = loy, whiy = hiy;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        wlox = fminf(wlox, __shfl_xor(wlox, off));
+        whix = fmaxf(whix, __shfl_xor(whix, off));
+        wloy = fminf(wloy, __shfl_xor(wloy, off));
+        whiy = fmaxf(whiy, __shfl_xor(whiy, off));
+    }
+    for (;;) {
+        unsigned long long hits = __ballot(p >= 0 && px >= wlox && px <= whix && py >= wloy && py <= whiy);
+        while (hits) {
+            const int b = __ffsll((long long)hits) - 1;
+            hits &= hits - 1;
+            const float qx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(px), b));
+            const float qy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(py), b));
+            const int q = __builtin_amdgcn_readlane(p, b);
+            unsigned long long key = TL_NONE;
+            if (qx >= lox && qx <= hix && qy >= loy && qy <= hiy) {
+                float u, v;
+                if (ts_solve_cell(c, qx, qy, u, v))
+                    key = ts_locate_key(ts_mix(ta.z, tb.z, tc.z, td.z, u, v), ts_mix(ta.w, tb.w, tc.w, td.w, u, v), thr, cell);
+            }
+            if (__any(key != TL_NONE)) {
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) {
+                    const unsigned long long other = __shfl_xor(key, off);
+                    key = other < key ? other : key;
+                }
+                if (lane == 0) atomicMin(keys + q, key);
+            }
+        }
+        k0 += 64;
+        if (k0 >= k_end) break;
+        p = k0 + lane < k_end ? order[k0 + lane] : -1;
+        if (p >= 0) { px = xy[2 * (long long)p]; py = xy[2 * (long long)p + 1]; }
+    }
+}
+
+// One lane per query, in the caller's order: the winning cell solved again with the same device function.
+__global__ __launch_bounds__(256) void ts_locate_resolve_kernel(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
+                                                                const int *__restrict__ group_of, int H, int W, int N,
+                                                                const float *__restrict__ xy, const unsigned long long *__restrict__ keys,
+                                                                float *__restrict__ table, int *__restrict__ cell_out) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    const unsigned long long key = keys[n];
+    const float nan = __uint_as_float(0x7fc00000u);
+    float4 row = make_float4(nan, nan, nan, nan);
+    int cell = -1;
+    if (key != TL_NONE && (key & 0xffffffffull) < (unsigned long long)(H - 1) * (W - 1)) {     // (only cells of the frame are ever keyed)
+        cell = (int)(unsigned)(key & 0xffffffffull);
+        const int g = group_of[n];
+        const int i = cell / (W - 1), j = cell % (W - 1);
+        const uint2 *__restrict__ frame = frames[g];
+        const Dec4 dec(lohis[g]);
+        const long long o = (long long)i * W + j;
+        const float4 ta = dec(frame[o]), tb = dec(frame[o + 1]), tc = dec(frame[o + W]), td = dec(frame[o + W + 1]);
+        const LocCell c = {(float)j + ta.x, (float)i + ta.y, (float)(j + 1) + tb.x, (float)i + tb.y,
+                           (float)j + tc.x, (float)(i + 1) + tc.y, (float)(j + 1) + td.x, (float)(i + 1) + td.y};
+        float u, v;
+        ts_solve_cell(c, xy[2 * (long long)n], xy[2 * (long long)n + 1], u, v);
+        row = make_float4((float)j + u, (float)i + v, ts_mix(ta.z, tb.z, tc.z, td.z, u, v), ts_mix(ta.w, tb.w, tc.w, td.w, u, v));
+    }
+    *reinterpret_cast<float4 *>(table + 4 * (long long)n) = row;
+    cell_out[n] = cell;
+}
+
 static int ts_blocks(long long n) {
     const long long b = (n + (long long)TS_T * TS_PX - 1) / ((long long)TS_T * TS_PX);
     return (int)(b < 1 ? 1 : (b > TS_B_MAX ? TS_B_MAX : b));
@@ -301,4 +464,36 @@ extern "C" int mftx_trackstore_query(const uint16_t *const *chunks, const float 
         if (rc) return rc;
     }
     return 0;
+}
+
+extern "C" int mftx_trackstore_locate(const uint16_t *const *frames, const float *const *lohis, const int *group_start, int G,
+                                      const int *order, const int *group_of, int H, int W, int N, const float *xy,
+                                      float occlusion_threshold, unsigned long long *keys, float *table, int *cell, void *stream) {
+    if (N < 0 || G < 0) return fail(MFTX_E_ARG, "trackstore_locate: need N >= 0, G >= 0");
+    if (H < 2 || W < 2) return fail(MFTX_E_ARG, "trackstore_locate: H and W must be >= 2");
+    if (N == 0) return 0;
+    if (!frames || !lohis || !group_start || !order || !group_of || !xy || !keys || !table || !cell)
+        return fail(MFTX_E_ARG, "trackstore_locate: null pointer");
+    if (G < 1 || G > N) return fail(MFTX_E_ARG, "trackstore_locate: need 1 <= G <= N frame groups");
+    if ((long long)(H - 1) * (W - 1) > 0x7fffffffLL) return fail(MFTX_E_ARG, "trackstore_locate: more than 2^31 - 1 cells");
+    const int tiles_x = cdiv(W - 1, TL_TW), tiles_y = cdiv(H - 1, TL_TH);
+    const long long tiles = (long long)tiles_x * tiles_y;
+    if (tiles * G > 0x7fffffffLL) return fail(MFTX_E_ARG, "trackstore_locate: %lld cell tiles x %d frame groups exceed one grid", tiles, G);
+    if (!aligned_to(frames, 8) || !aligned_to(lohis, 8) || !aligned_to(keys, 8))
+        return fail(MFTX_E_ALIGN, "trackstore_locate: the pointer tables and the keys must be 8-byte aligned");
+    if (!aligned_to(group_start, 4) || !aligned_to(order, 4) || !aligned_to(group_of, 4) || !aligned_to(xy, 4) || !aligned_to(cell, 4))
+        return fail(MFTX_E_ALIGN, "trackstore_locate: group_start, order, group_of, xy and cell must be 4-byte aligned");
+    if (!aligned16(table)) return fail(MFTX_E_ALIGN, "trackstore_locate: the table must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    // per tile and group: 33 x 9 packed corners; per query: its coordinates in every wave, a key, a row, a cell index
+    ProfScope prof(PC_CHAIN, s, 8.0 * (TL_TW + 1) * (TL_TH + 1) * (double)tiles * G + (8.0 + 8.0 + 16.0 + 4.0) * (double)N);
+    hipError_t e = hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * (size_t)N, s);
+    if (e != hipSuccess) return fail((int)e, "trackstore_locate: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(ts_locate_search_kernel, dim3((unsigned)(tiles * G)), dim3(256), 0, s, reinterpret_cast<const uint2 *const *>(frames),
+                       lohis, group_start, order, tiles_x, (int)tiles, H, W, xy, occlusion_threshold, keys);
+    int rc = check_launch("trackstore_locate");
+    if (rc) return rc;
+    hipLaunchKernelGGL(ts_locate_resolve_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, reinterpret_cast<const uint2 *const *>(frames), lohis,
+                       group_of, H, W, N, xy, keys, table, cell);
+    return check_launch("trackstore_locate");
 }

@@ -13,6 +13,7 @@ import ctypes as C
 import math
 from typing import NamedTuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1015,6 +1016,70 @@ def trackstore_query(chunks, lohi_chunks, slots, xy, table, column0=0):
                                     _chk(xy, "xy"), _chk(table, "table"), 4 * int(table.shape[1]), int(column0), _stream()),
           "mftx_trackstore_query")
     return table
+
+
+def locate_tables(point_slots, chunk_ptrs, lohi_ptrs, frames_per_chunk, frame_bytes):
+    """The tables of ``mftx_trackstore_locate`` for N queries whose frames sit in the slots ``point_slots`` (host integers, any
+    order) as ONE int64 host array, and where its parts begin: -> (buf, G, (frames, lohis, group_start, order, group_of) byte
+    offsets).  Queries are grouped by slot (stable, slots ascending): frames / lohis [G] addresses (``chunk_ptrs[c]`` +
+    the frame's offset in its chunk), then int32 group_start [G + 1], order [N], group_of [N]."""
+    slots = np.asarray(point_slots, dtype=np.int64).reshape(-1)
+    N = int(slots.shape[0])
+    order = np.argsort(slots, kind="stable")
+    sorted_slots = slots[order]
+    first = np.flatnonzero(np.concatenate([[True], sorted_slots[1:] != sorted_slots[:-1]]))
+    G = int(first.shape[0])
+    group_slot = sorted_slots[first]
+    group_of = np.empty(N, np.int32)
+    group_of[order] = np.repeat(np.arange(G, dtype=np.int32), np.diff(np.concatenate([first, [N]])))
+    chunk, within = group_slot // frames_per_chunk, group_slot % frames_per_chunk
+    n32 = (G + 1) + 2 * N
+    buf = np.zeros(2 * G + (n32 + 1) // 2, np.int64)
+    buf[0:G] = np.asarray(chunk_ptrs, dtype=np.int64)[chunk] + within * frame_bytes
+    buf[G:2 * G] = np.asarray(lohi_ptrs, dtype=np.int64)[chunk] + within * 32
+    tail = buf[2 * G:].view(np.int32)
+    tail[0:G] = first
+    tail[G] = N
+    tail[G + 1:G + 1 + N] = order
+    tail[G + 1 + N:G + 1 + 2 * N] = group_of
+    return buf, G, (0, 8 * G, 16 * G, 16 * G + 4 * (G + 1), 16 * G + 4 * (G + 1) + 4 * N)
+
+
+def trackstore_locate(chunks, lohi_chunks, point_slots, xy, table, cell, occlusion_threshold=0.5):
+    """The stored map inverted at points given on stored frames, in one call (``mftx_trackstore_locate``).  chunks /
+    lohi_chunks as for ``trackstore_query``; point_slots: N HOST integers, the slot of the frame each point is given on (any
+    order, repeats welcome); xy [N,2] float32 on the device.  Row n of ``table`` (float32 device [N,4]) receives the template
+    point (x, y) whose image on that frame is xy[n], and occlusion and sigma there; ``cell`` (int32 device [N]) the template
+    cell it lies in, -1 (and a row of NaN) where nothing maps to xy[n].  The group tables go up through one pinned buffer;
+    no host synchronisation.  Returns (table, cell)."""
+    lib = _lib.load()
+    chunks, lohi_chunks = list(chunks), list(lohi_chunks)
+    if not chunks or len(chunks) != len(lohi_chunks):
+        raise MftxError("trackstore_locate: as many lohi tables as chunks, at least one")
+    fpc, H, W = (int(s) for s in chunks[0].shape[:3])
+    for c, l in zip(chunks, lohi_chunks):
+        if tuple(c.shape) != (fpc, H, W, 4) or tuple(l.shape) != (fpc, 4, 2):
+            raise MftxError("trackstore_locate: chunks must be [frames_per_chunk,H,W,4] with lohi [frames_per_chunk,4,2]")
+    if xy.dim() != 2 or int(xy.shape[1]) != 2:
+        raise MftxError("trackstore_locate: xy must be [N, 2]")
+    N = int(xy.shape[0])
+    slots = np.asarray(point_slots, dtype=np.int64).reshape(-1)
+    if int(slots.shape[0]) != N or (N and (slots.min() < 0 or slots.max() >= fpc * len(chunks))):
+        raise MftxError("trackstore_locate: point_slots must be N slots of the store")
+    if tuple(table.shape) != (N, 4) or tuple(cell.shape) != (N,):
+        raise MftxError("trackstore_locate: the table must be [N, 4], cell [N]")
+    cptr = [_chk(c, "chunk", torch.uint16) for c in chunks]
+    lptr = [_chk(l, "lohi chunk") for l in lohi_chunks]
+    xp, tp, cp = _chk(xy, "xy"), _chk(table, "table"), _chk(cell, "cell", torch.int32)
+    if N == 0:
+        return table, cell
+    buf, G, off = locate_tables(slots, cptr, lptr, fpc, H * W * 8)
+    tables = torch.from_numpy(buf).pin_memory().to(xy.device, non_blocking=True)
+    keys = torch.empty(N, dtype=torch.int64, device=xy.device)
+    base = tables.data_ptr()
+    check(lib.mftx_trackstore_locate(base + off[0], base + off[1], base + off[2], G, base + off[3], base + off[4], H, W, N, xp,
+                                     float(occlusion_threshold), keys.data_ptr(), tp, cp, _stream()), "mftx_trackstore_locate")
+    return table, cell
 
 
 class RaftEngine:

@@ -13,6 +13,8 @@ flow that passes through its disk cache: half a quantisation step of each channe
     table = store.query(points)                       # device [N, T, 4]: x, y, occlusion, sigma per frame, append order
     coords, occl = store.tracks(points, frames=[...]) # numpy, the shape MultiTemplateMFT.point_tracks() gives
     result = store.result(frame_i)                    # the dequantised FlowOUTrackingResult, on the device
+    table, cell = store.locate(points_on_57, 57)      # the stored map inverted: template x, y, occlusion, sigma; cell -1 = none
+    coords, occl, found = store.tracks_from(points_on_57, 57)     # ... and those template points followed over the frames
 
 ``device="cpu"`` is a host restatement of the same operations (numpy / torch), which pins the semantics without a GPU.
 """
@@ -42,6 +44,85 @@ def decompress_channel(q, lo, hi):
     """The inverse: uint16 array + the channel's (min, max) -> float32."""
     lo, hi = np.float32(lo), np.float32(hi)
     return (np.asarray(q).astype(np.float32) / U16_MAX) * (hi - lo) + lo
+
+
+# ---- locate: the stored map inverted at a point given on a stored frame -------------------------------------------------------
+# The definition (DESIGN.md, "locate"), in numpy float32 with + - * / only and in the order csrc/trackstore.hip (ts_solve_cell,
+# ts_mix, ts_locate_key) evaluates it: the two agree bit for bit (tests/test_gpu_track_locate.py).
+LOCATE_EPS = np.float32(2.0 ** -10)       # px: the widening of a cell's box and the residual a candidate may have
+LOCATE_NEWTON_STEPS = 6
+_ONE, _ZERO, _HALF = np.float32(1), np.float32(0), np.float32(0.5)
+
+
+def _clamp01(t):
+    return np.where(t < _ZERO, _ZERO, np.where(t > _ONE, _ONE, t))        # (a NaN stays one)
+
+
+def _solve_cells(c, qx, qy):
+    """c = (ax, ay, bx, by, cx, cy, dx, dy): float32 [K] corner images A = M(i, j), B = M(i, j+1), C = M(i+1, j), D = M(i+1, j+1) of
+    K cells; (qx, qy): the query, float32 scalars -> (u [K], v [K], candidate [K]): the clamped solution of
+    A + u (B - A) + v (C - A) + u v (A - B - C + D) = Q after LOCATE_NEWTON_STEPS Newton steps from the cell's centre."""
+    ax, ay, bx, by, cx, cy, dx, dy = c
+    ex, ey, gx, gy = bx - ax, by - ay, cx - ax, cy - ay
+    hx, hy = ((ax - bx) - cx) + dx, ((ay - by) - cy) + dy
+    u = np.full(ax.shape, _HALF, np.float32)
+    v = u.copy()
+    with np.errstate(all="ignore"):
+        for _ in range(LOCATE_NEWTON_STEPS):
+            uv = u * v
+            rx = (((ax + u * ex) + v * gx) + uv * hx) - qx
+            ry = (((ay + u * ey) + v * gy) + uv * hy) - qy
+            j00, j01, j10, j11 = ex + v * hx, gx + u * hx, ey + v * hy, gy + u * hy
+            det = j00 * j11 - j01 * j10
+            du, dv = (rx * j11 - ry * j01) / det, (ry * j00 - rx * j10) / det
+            u, v = u - du, v - dv
+        finite = np.isfinite(u) & np.isfinite(v)
+        u, v = _clamp01(u), _clamp01(v)
+        uv = u * v
+        rx = (((ax + u * ex) + v * gx) + uv * hx) - qx
+        ry = (((ay + u * ey) + v * gy) + uv * hy) - qy
+        ok = finite & (np.abs(rx) <= LOCATE_EPS) & (np.abs(ry) <= LOCATE_EPS)
+    return u, v, ok
+
+
+def _mix(a, b, c, d, u, v):
+    """The sampler's weights (1-u)(1-v), u(1-v), (1-u)v, uv and its order of summation."""
+    w00, w01, w10, w11 = (_ONE - u) * (_ONE - v), u * (_ONE - v), (_ONE - u) * v, u * v
+    return a * w00 + b * w01 + c * w10 + d * w11
+
+
+def _locate_host(planes, q, thr, table, cell):
+    """planes = (fx, fy, occlusion, sigma) float32 [H, W] of ONE dequantised frame; q float32 [K, 2] -> rows of table [K, 4] and
+    cell [K] (numpy, written in place)."""
+    fx, fy, oc, sg = planes
+    H, W = fx.shape
+    mx = np.arange(W, dtype=np.float32)[None, :] + fx
+    my = np.arange(H, dtype=np.float32)[:, None] + fy
+
+    def corners(p):
+        return p[:-1, :-1].ravel(), p[:-1, 1:].ravel(), p[1:, :-1].ravel(), p[1:, 1:].ravel()
+
+    (ax, bx, cx, dx), (ay, by, cy, dy) = corners(mx), corners(my)
+    lox, hix = np.fmin(np.fmin(ax, bx), np.fmin(cx, dx)) - LOCATE_EPS, np.fmax(np.fmax(ax, bx), np.fmax(cx, dx)) + LOCATE_EPS
+    loy, hiy = np.fmin(np.fmin(ay, by), np.fmin(cy, dy)) - LOCATE_EPS, np.fmax(np.fmax(ay, by), np.fmax(cy, dy)) + LOCATE_EPS
+    occ, sig = corners(oc), corners(sg)
+    for n in range(q.shape[0]):
+        qx, qy = q[n, 0], q[n, 1]
+        table[n], cell[n] = np.nan, -1
+        idx = np.flatnonzero((qx >= lox) & (qx <= hix) & (qy >= loy) & (qy <= hiy))       # the prefilter
+        if idx.size == 0:
+            continue
+        u, v, ok = _solve_cells((ax[idx], ay[idx], bx[idx], by[idx], cx[idx], cy[idx], dx[idx], dy[idx]), qx, qy)
+        if not ok.any():
+            continue
+        idx, u, v = idx[ok], u[ok], v[ok]
+        o = _mix(*(p[idx] for p in occ), u, v)
+        s = _mix(*(p[idx] for p in sig), u, v)
+        key_sigma = np.where(s > _ZERO, s, _ZERO)           # what the device key holds: a sigma that is not > 0 counts as +0
+        w = np.lexsort((idx, key_sigma, o > thr))[0]        # smallest (occluded, sigma, cell)
+        i, j = divmod(int(idx[w]), W - 1)
+        table[n] = (np.float32(j) + u[w], np.float32(i) + v[w], o[w], s[w])
+        cell[n] = idx[w]
 
 
 class DenseTrackStore:
@@ -192,3 +273,63 @@ class DenseTrackStore:
         """The stored frame, dequantised: a ``FlowOUTrackingResult`` on the store's device (for ``draw_edit`` /
         ``warp_forward_device`` after the fact, and for export)."""
         return self._result_of_slot(self.slot_of(frame_i))
+
+    # ------------------------------------------------------------------ the inverse: points given on a stored frame
+    def locate(self, points, frame, occlusion_threshold=0.5, out=None):
+        """points (N, 2) xy given ON stored frame(s) ``frame`` -- one frame id, or a host sequence of N ids, any order -> (table,
+        cell) on the store's device: float32 [N, 4] = (template x, template y, occlusion, sigma) of the template point whose
+        image on that frame is the query, and int32 [N] = the template cell i * (W - 1) + j it lies in.  Where several
+        template points map to the query the one that is not occluded (occlusion <= ``occlusion_threshold``), then of lowest
+        sigma, then of lowest cell wins; where none does, cell is -1 and the row is NaN.  ``out``: a (table, cell) pair to
+        write into.  On the device: one call, and with ``points`` a device tensor no host synchronisation."""
+        if not isinstance(points, torch.Tensor):
+            points = torch.from_numpy(np.ascontiguousarray(np.asarray(points, dtype=np.float32)))
+        if points.dim() != 2 or int(points.shape[1]) != 2:
+            raise ValueError(f"DenseTrackStore.locate: points must be (N, 2), not {tuple(points.shape)}")
+        xy = points.to(device=self.device, dtype=torch.float32).contiguous()
+        N = int(xy.shape[0])
+        ids = np.asarray(frame)
+        if ids.ndim == 0:
+            slots = [self.slot_of(ids)] * N                    # KeyError for a frame that was never appended
+        elif ids.ndim == 1 and ids.shape[0] == N:
+            slots = [self.slot_of(f) for f in ids]
+        else:
+            raise ValueError(f"DenseTrackStore.locate: frame must be one frame id or {N} of them")
+        if out is None:
+            out = (torch.empty((N, 4), dtype=torch.float32, device=self.device), torch.empty((N,), dtype=torch.int32, device=self.device))
+        table, cell = out
+        if tuple(table.shape) != (N, 4) or table.dtype != torch.float32 or tuple(cell.shape) != (N,) or cell.dtype != torch.int32 \
+                or table.device != xy.device or cell.device != xy.device or not table.is_contiguous() or not cell.is_contiguous():
+            raise ValueError(f"DenseTrackStore.locate: out must be contiguous (float32 [{N}, 4], int32 [{N}]) tensors on {self.device}")
+        if N == 0:
+            return table, cell
+        if self.native:
+            from . import ops
+            ops.trackstore_locate(self._chunks, self._lohi, slots, xy, table, cell, occlusion_threshold)
+        else:
+            q, slots = xy.numpy(), np.asarray(slots)
+            tb, cl = table.numpy(), cell.numpy()
+            for slot in np.unique(slots):
+                r = self._result_of_slot(int(slot))
+                planes = (r.flow[0].numpy(), r.flow[1].numpy(), r.occlusion[0].numpy(), r.sigma[0].numpy())
+                sel = np.flatnonzero(slots == slot)
+                t, c = np.empty((sel.size, 4), np.float32), np.empty(sel.size, np.int32)
+                _locate_host(planes, q[sel], np.float32(occlusion_threshold), t, c)
+                tb[sel], cl[sel] = t, c
+        return table, cell
+
+    def tracks_from(self, points, frame, frames=None, occlusion_threshold=0.5):
+        """points given on stored frame(s) ``frame`` (as for ``locate``), followed over ``frames`` (default: all, in append
+        order) -> numpy (coords [N, T, 2], occlusion [N, T], found [N]): ``locate``, then ``query`` of the located template
+        points.  A point that no template point maps to has found False, NaN coordinates and occlusion 1.  ONE download; it
+        synchronises."""
+        table, cell = self.locate(points, frame, occlusion_threshold)
+        found = cell >= 0
+        template = torch.where(found[:, None], table[:, 0:2], torch.zeros((), dtype=torch.float32, device=self.device))
+        tracks = self.query(template, frames)
+        N, T = int(tracks.shape[0]), int(tracks.shape[1])
+        both = torch.cat([tracks.reshape(N, T * 4), found.to(torch.float32)[:, None]], dim=1).cpu().numpy()
+        tracks, found = both[:, :T * 4].reshape(N, T, 4), both[:, T * 4] > 0
+        coords, occl = tracks[:, :, 0:2].copy(), tracks[:, :, 2].copy()
+        coords[~found], occl[~found] = np.nan, 1.0
+        return coords, occl, found
