@@ -87,7 +87,10 @@ def bilinear_zeros(img, ix, iy):
     Returns (C, ...).  Semantics of ``F.grid_sample(mode='bilinear',
     padding_mode='zeros', align_corners=True)``: the 4 integer neighbours of
     (ix, iy) contribute with weights (1-fx)(1-fy).. and any neighbour outside
-    [0,W-1]x[0,H-1] contributes 0.
+    [0,W-1]x[0,H-1] contributes 0 -- whatever lies at the clamped address it is
+    read from here (grid_sample does not read it: a NaN or inf on the border
+    does not reach a sample whose tap is outside).  A neighbour inside the image
+    takes part even with a zero weight (inf * 0 = NaN), as in grid_sample.
     """
     C, H, W = img.shape
     x0 = torch.floor(ix)
@@ -105,7 +108,7 @@ def bilinear_zeros(img, ix, iy):
             ok = (xx >= 0) & (xx <= W - 1) & (yy >= 0) & (yy <= H - 1)
             idx = (yy.clamp(0, H - 1) * W + xx.clamp(0, W - 1)).reshape(-1)
             v = flat[:, idx].reshape((C,) + tuple(ix.shape))
-            out = out + v * (wx * wy * ok.to(F32))
+            out = out + torch.where(ok, v, torch.zeros_like(v)) * (wx * wy)
     return out
 
 
@@ -474,10 +477,11 @@ def select(cands, thr):
     scores = -sigs
     scores = torch.where(occs > thr, torch.full_like(scores, -float("inf")), scores)
     K = len(cands)
-    # first maximal index along dim 0
+    # first maximal index along dim 0; a NaN score beats every number and the first NaN is kept (Tensor.max(dim=0).indices):
+    # where there is a NaN, `best` is NaN and equals nothing
     best = scores.max(dim=0, keepdim=True).values
     ks = torch.arange(K).reshape(K, 1, 1, 1).expand_as(scores)
-    idx = torch.where(scores == best, ks, torch.full_like(ks, K)).min(dim=0, keepdim=True).values
+    idx = torch.where((scores == best) | torch.isnan(scores), ks, torch.full_like(ks, K)).min(dim=0, keepdim=True).values
     flow = flows.gather(0, idx.expand(1, 2, *idx.shape[2:]))[0]
     occ = occs.gather(0, idx)[0].clone()
     sig = sigs.gather(0, idx)[0]

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import chain_reference
 import golden_inputs as gi
 from oracle import mft_oracle as O
 
@@ -649,11 +650,16 @@ def test_chain_select_packed_and_vec4_bitwise(ops_mod):
     for a, b, c in zip(v4, pk, sc):
         assert torch.equal(a, b) and torch.equal(a, c)
     want = O.select([O.chain(tuple(t.cpu() for t in L), tuple(t.cpu() for t in R)) for L, R in zip(Ls, Rs)], thr)
-    assert (v4[3].cpu().long() == want[3]).float().mean() > 0.999
+    # the selection is exact given its candidates: the fused result equals the reference rule (tests/chain_reference.py) applied
+    # to the GPU's own chained candidates, bit for bit at every pixel
+    cands = [ops_mod.chain(L, R) for L, R in zip(Ls, Rs)]
+    exact = chain_reference.select_ref([tuple(t.cpu().numpy() for t in c) for c in cands], thr)
+    for got, ref in zip(v4, exact):
+        got = got.cpu().numpy()
+        assert got.shape == ref.shape and np.array_equal(chain_reference.bits(got), chain_reference.bits(ref.astype(got.dtype)))
     same = v4[3].cpu().long() == want[3]
     assert (v4[0].cpu() - want[0]).abs().max(0).values[same].max() < 2e-4
     # select alone: vec4 == scalar
-    cands = [ops_mod.chain(L, R) for L, R in zip(Ls, Rs)]
     s4 = ops_mod.select(cands, thr, want_chosen=True)
     s1 = ops_mod.select([tuple(misaligned(t) for t in c) for c in cands], thr, want_chosen=True)
     for a, b, c in zip(s4, s1, v4):
