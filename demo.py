@@ -2,7 +2,7 @@
 """Track every pixel of a video with MFT and write the point / edit overlays -- the reference's ``demo.py`` on
 the MI355X engine.
 
-    python demo.py --video <dir of PNG frames | frames.npy> [--edit edit.png] [--out demo_out/] [--synthetic] [--gpu-overlays | --track-store [--query-frame Q]]
+    python demo.py --video <dir of PNG frames | frames.npy> [--edit edit.png] [--out demo_out/] [--synthetic] [--gpu-overlays | --track-store [--query-frame Q] [--edit-frame Q]]
 
 Differences forced by the environment: no OpenCV here, so the input is a directory of PNG frames or a ``.npy``
 frame array (video containers work when cv2 is importable) and the overlays are written as numbered PNGs instead of
@@ -13,7 +13,9 @@ arrive: no dense result is downloaded or kept.  With ``--track-store`` the track
 16 bits (``mft_amd/trackstore.py``: 8 bytes per pixel) and nothing is downloaded inside the loop; afterwards ONE read-out gives the
 points of all frames, and the edit overlay is drawn from the stored frames.  ``--query-frame Q`` takes the query grid on frame Q
 instead of frame 0: the stored map of frame Q is inverted at the grid (``DenseTrackStore.tracks_from``), and grid points that no
-template point maps to are drawn as occluded.
+template point maps to are drawn as occluded.  ``--edit-frame Q`` takes the RGBA edit as painted on frame Q instead of frame 0:
+every frame's overlay is then splatted along the dense flow from frame Q to it (``DenseTrackStore.result_from``: frame Q's stored
+map inverted at every pixel, then followed forward), and pixels of frame Q that no template point maps to carry no edit.
 """
 import argparse
 import logging
@@ -47,6 +49,7 @@ def parse_arguments():
     ap.add_argument('--gpu-overlays', action='store_true', help='render the overlays on the GPU while tracking; dense results stay on the device')
     ap.add_argument('--track-store', action='store_true', help='keep every dense result on the GPU in 16 bits; read the points out after the pass')
     ap.add_argument('--query-frame', type=int, default=None, metavar='Q', help='with --track-store: take the query grid on frame Q instead of frame 0')
+    ap.add_argument('--edit-frame', type=int, default=None, metavar='Q', help='with --track-store: the edit is painted on frame Q instead of frame 0')
     return ap.parse_args()
 
 
@@ -62,8 +65,8 @@ def run(args):
         if args.gpu_overlays:
             raise SystemExit("--track-store and --gpu-overlays are two ways to avoid the per-frame download: choose one")
         config.track_store = True
-    elif args.query_frame is not None:
-        raise SystemExit("--query-frame reads the track store: give --track-store too")
+    elif args.query_frame is not None or args.edit_frame is not None:
+        raise SystemExit("--query-frame and --edit-frame read the track store: give --track-store too")
     tracker = config.tracker_class(config)
     if args.synthetic:
         from mft_amd.synth import SyntheticVideo
@@ -109,7 +112,8 @@ def run(args):
 
 def run_track_store(args, tracker, frames, name):
     """The tracker keeps the dense results (``config.track_store``): the loop only tracks.  Afterwards one ``tracks()`` call reads
-    the query grid out of all stored frames, and ``store.result(i)`` dequantises a frame on the device for the edit overlay."""
+    the query grid out of all stored frames, and ``store.result(i)`` dequantises a frame on the device for the edit overlay
+    (``store.result_from(Q, i)`` where the edit is painted on frame Q)."""
     up = [torch.cuda.current_stream()]
     if getattr(tracker.flower, "_enc_stream", None) is not None:
         up.append(tracker.flower._enc_stream)
@@ -130,7 +134,13 @@ def run_track_store(args, tracker, frames, name):
     for i, frame in enumerate(frames):
         vio.imwrite_bgr(args.out / f"{name}_points" / f"{i:05d}.png", vis.draw_dots(frame, coords[:, i], occlusions[:, i]))
         if edit is not None:
-            vio.imwrite_bgr(args.out / f"{name}_edit" / f"{i:05d}.png", vis.draw_edit(frame, store.result(i), edit))
+            if args.edit_frame is None:
+                result = store.result(i)
+            else:                     # frame Q -> frame i; a pixel of frame Q that nothing maps to counts as occluded: no edit there
+                result, found = store.result_from(args.edit_frame, i)
+                if i == 0:
+                    logger.info("edit on frame %d: %d of %d pixels are images of template points", args.edit_frame, int(found.sum()), found.numel())
+            vio.imwrite_bgr(args.out / f"{name}_edit" / f"{i:05d}.png", vis.draw_edit(frame, result, edit))
     logger.info("wrote %s", args.out)
     return 0
 

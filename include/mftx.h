@@ -646,6 +646,25 @@ int mftx_trackstore_locate(const uint16_t *const *frames, const float *const *lo
                            const int *order, const int *group_of, int H, int W, int N, const float *xy,
                            float occlusion_threshold, unsigned long long *keys, float *table, int *cell, void *stream);
 
+/* G stored frames inverted DENSELY: mftx_trackstore_locate with the H * W pixel centres (x, y), x = 0 .. W - 1, y = 0 .. H - 1,
+ * row-major, as the queries of every frame -- the same candidate rule, key and resolve step, so bit for bit the same rows and
+ * cells -- computed the other way round: every template cell writes its key onto the pixel centres that its widened box
+ * holds.  Work grows with the cells plus the area of their boxes instead of cells x pixels, each frame is read once, and no
+ * query or group tables are needed.  DEVICE memory:
+ *   frames [G] / lohis [G]: as for mftx_trackstore_locate (pointer tables, 8-byte aligned);
+ *   keys [G * H * W] 64-bit words (8-byte aligned): workspace, set to all ones by this call, then one 64-bit integer atomic
+ *   minimum per candidate (cell, pixel) pair;
+ *   table [G][H][W][4] float32 (16-byte aligned): template x, template y, occlusion, sigma of the template point whose image is
+ *   pixel (y, x) of frame g; cell [G][H][W] int32: its cell i * (W - 1) + j, or -1 with four NaNs (0x7fc00000) where nothing
+ *   maps to that pixel.
+ * A cell's box is turned into a pixel range after its bounds were limited to the frame in float, so infinite, NaN or huge
+ * corner images give an empty or a frame-sized range; a cell whose range holds more than 16 centres is walked by its whole
+ * wave, 64 centres at a time.  One memset and two launches whatever G is; no allocation, no synchronisation.  H * W < 2^31.
+ * G == 0: nothing is done, 0 is returned. */
+int mftx_trackstore_invert(const uint16_t *const *frames, const float *const *lohis, int G, int H, int W,
+                           float occlusion_threshold, unsigned long long *keys /* [G*H*W] */,
+                           float *table, int *cell, void *stream);
+
 /* ---- 8f-4: frame / result transport without copy queues -------------------------------------------------------------------
  * A copy KERNEL: src -> dst, n bytes, both 16-byte aligned; either may be PINNED HOST memory (hipHostMalloc / torch
  * pin_memory: mapped into the device's address space), which a kernel reads and writes over PCIe directly.  Unlike

@@ -145,6 +145,8 @@ SIGNATURES = {
                                         C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
     "mftx_trackstore_locate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                          C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mftx_trackstore_invert": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
     "mftx_png_unfilter":(C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "mftx_copy_bytes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
 }

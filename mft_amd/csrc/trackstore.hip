@@ -11,6 +11,8 @@
 //   locate : the inverse -- points given ON stored frames -> the template points they are the images of: a search over the
 //            template's cells (bilinear patches solved by Newton steps, the winner a 64-bit integer atomic minimum) and a resolve
 //            kernel.  Bitwise the numpy float32 restatement in mft_amd/trackstore.py.
+//   invert : locate at every pixel centre of stored frames, as a scatter: each template cell writes its key onto the pixel
+//            centres its box holds; the same resolve.  Bitwise locate with the pixel grid as its queries.
 //
 // Planes are read and written one float per lane (four pixels per thread in flight): their bases need 4-byte alignment only
 // (flow y of a [2][H][W] tensor and the planes of a [4][H][W] buffer sit H * W floats apart, which is no multiple of 16
@@ -352,32 +354,145 @@ __global__ __launch_bounds__(256) void ts_locate_search_kernel(const uint2 *cons
     }
 }
 
-// One lane per query, in the caller's order: the winning cell solved again with the same device function.
+// The answer to one query (qx, qy) on frame g from its key: the winning cell solved again with the same device function.
+// -> the cell, -1 (and a row of NaN) where the key names none.
+__device__ __forceinline__ int ts_resolve(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis, int g, int H,
+                                          int W, unsigned long long key, float qx, float qy, float4 &row) {
+    const float nan = __uint_as_float(0x7fc00000u);
+    row = make_float4(nan, nan, nan, nan);
+    if (key == TL_NONE || (key & 0xffffffffull) >= (unsigned long long)(H - 1) * (W - 1)) return -1;     // (only cells of the frame are ever keyed)
+    const int cell = (int)(unsigned)(key & 0xffffffffull);
+    const int i = cell / (W - 1), j = cell % (W - 1);
+    const uint2 *__restrict__ frame = frames[g];
+    const Dec4 dec(lohis[g]);
+    const long long o = (long long)i * W + j;
+    const float4 ta = dec(frame[o]), tb = dec(frame[o + 1]), tc = dec(frame[o + W]), td = dec(frame[o + W + 1]);
+    const LocCell c = {(float)j + ta.x, (float)i + ta.y, (float)(j + 1) + tb.x, (float)i + tb.y,
+                       (float)j + tc.x, (float)(i + 1) + tc.y, (float)(j + 1) + td.x, (float)(i + 1) + td.y};
+    float u, v;
+    ts_solve_cell(c, qx, qy, u, v);
+    row = make_float4((float)j + u, (float)i + v, ts_mix(ta.z, tb.z, tc.z, td.z, u, v), ts_mix(ta.w, tb.w, tc.w, td.w, u, v));
+    return cell;
+}
+
+// One lane per query, in the caller's order.
 __global__ __launch_bounds__(256) void ts_locate_resolve_kernel(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
                                                                 const int *__restrict__ group_of, int H, int W, int N,
                                                                 const float *__restrict__ xy, const unsigned long long *__restrict__ keys,
                                                                 float *__restrict__ table, int *__restrict__ cell_out) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
-    const unsigned long long key = keys[n];
-    const float nan = __uint_as_float(0x7fc00000u);
-    float4 row = make_float4(nan, nan, nan, nan);
-    int cell = -1;
-    if (key != TL_NONE && (key & 0xffffffffull) < (unsigned long long)(H - 1) * (W - 1)) {     // (only cells of the frame are ever keyed)
-        cell = (int)(unsigned)(key & 0xffffffffull);
-        const int g = group_of[n];
-        const int i = cell / (W - 1), j = cell % (W - 1);
-        const uint2 *__restrict__ frame = frames[g];
-        const Dec4 dec(lohis[g]);
-        const long long o = (long long)i * W + j;
-        const float4 ta = dec(frame[o]), tb = dec(frame[o + 1]), tc = dec(frame[o + W]), td = dec(frame[o + W + 1]);
-        const LocCell c = {(float)j + ta.x, (float)i + ta.y, (float)(j + 1) + tb.x, (float)i + tb.y,
-                           (float)j + tc.x, (float)(i + 1) + tc.y, (float)(j + 1) + td.x, (float)(i + 1) + td.y};
-        float u, v;
-        ts_solve_cell(c, xy[2 * (long long)n], xy[2 * (long long)n + 1], u, v);
-        row = make_float4((float)j + u, (float)i + v, ts_mix(ta.z, tb.z, tc.z, td.z, u, v), ts_mix(ta.w, tb.w, tc.w, td.w, u, v));
-    }
+    float4 row;
+    const int cell = ts_resolve(frames, lohis, group_of[n], H, W, keys[n], xy[2 * (long long)n], xy[2 * (long long)n + 1], row);
     *reinterpret_cast<float4 *>(table + 4 * (long long)n) = row;
+    cell_out[n] = cell;
+}
+
+// ---- invert: locate at EVERY pixel centre of a stored frame, the other way round ---------------------------------------------------
+// The search kernel's work is tiles x queries; with the H * W pixel centres as the queries a cell would be tested against every
+// pixel of the frame.  Here every template cell writes itself onto the few pixel centres its widened box can hold: the same box
+// test, the same ts_solve_cell, the same key, the same atomic minimum per query -- so the candidate sets, and with them the bits, are
+// those of locate on the pixel grid.  Work is the cells plus the area of their boxes, and each stored frame is read once.
+constexpr int TI_INLINE = 16;       // a cell whose clipped range holds at most this many centres is walked by its own lane
+
+// The pixel centres lo <= q <= hi can hold, as the integers a .. b clipped to 0 .. n - 1 (a superset: floor and ceil).  The bounds
+// are limited in FLOAT before they are converted: an infinite or huge bound gives the frame's edge, a NaN bound an empty range
+// (fmaxf / fminf return their other operand), never an undefined conversion.
+__device__ __forceinline__ void ts_centre_range(float lo, float hi, int n, int &a, int &b) {
+    a = (int)fminf(fmaxf(floorf(lo), 0.f), (float)n);
+    b = (int)fminf(fmaxf(ceilf(hi), -1.f), (float)(n - 1));
+    a = min(max(a, 0), n);          // ((float)n is n itself below 2^24; this keeps the range inside the frame beyond that too)
+    b = min(max(b, -1), n - 1);
+}
+
+__device__ __forceinline__ float ts_lane_f(float v, int b) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), b)); }
+
+struct InvCell {                    // what a lane (phase 1) or a whole wave (phase 2) needs of one cell
+    LocCell c;
+    float oa, ob, oc, od, sa, sb, sc, sd;      // the corners' occlusion and sigma
+    float lox, hix, loy, hiy;                  // the widened box
+    unsigned cell;
+};
+
+// the cell tested at pixel centre (x, y) of the frame whose keys start at `keys`: 0 <= x < W, 0 <= y < H is the caller's business
+__device__ __forceinline__ void ts_invert_try(const InvCell &t, int x, int y, int W, float thr, unsigned long long *__restrict__ keys) {
+    const float qx = (float)x, qy = (float)y;
+    if (qx >= t.lox && qx <= t.hix && qy >= t.loy && qy <= t.hiy) {
+        float u, v;
+        if (ts_solve_cell(t.c, qx, qy, u, v))
+            atomicMin(keys + ((long long)y * W + x),
+                      ts_locate_key(ts_mix(t.oa, t.ob, t.oc, t.od, u, v), ts_mix(t.sa, t.sb, t.sc, t.sd, u, v), thr, t.cell));
+    }
+}
+
+// Grid: cell tiles x frames (blockIdx.x = g * tiles + tile), a cell per lane, the tile's corners staged as the search kernel
+// stages them.  Phase 1: a lane whose range holds at most TI_INLINE centres walks it.  Phase 2: the wave takes the larger cells
+// one at a time, its 64 lanes striding over the range, so that a torn cell's frame-sized box costs area / 64 solves per lane.
+__global__ __launch_bounds__(256) void ts_invert_scatter_kernel(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
+                                                                int tiles_x, int tiles, int H, int W, float thr,
+                                                                unsigned long long *__restrict__ keys) {
+    __shared__ float4 corner[TL_TH + 1][TL_TW + 1];       // (M x, M y, occlusion, sigma) of the tile's corners
+    const int g = blockIdx.x / tiles, tile = blockIdx.x % tiles;
+    const int i0 = (tile / tiles_x) * TL_TH, j0 = (tile % tiles_x) * TL_TW;
+    const uint2 *__restrict__ frame = frames[g];
+    const int lane = threadIdx.x & 63;
+    const Dec4 dec(lohis[g]);
+    for (int e = threadIdx.x; e < (TL_TH + 1) * (TL_TW + 1); e += 256) {
+        const int ci = e / (TL_TW + 1), cj = e % (TL_TW + 1);
+        const int i = min(i0 + ci, H - 1), j = min(j0 + cj, W - 1);           // (a ragged tile's cells beyond the frame are never used)
+        const float4 t = dec(frame[(long long)i * W + j]);
+        corner[ci][cj] = make_float4((float)j + t.x, (float)i + t.y, t.z, t.w);
+    }
+    __syncthreads();
+    keys += (long long)g * H * W;
+    const int li = threadIdx.x / TL_TW, lj = threadIdx.x % TL_TW;
+    const bool active = i0 + li < H - 1 && j0 + lj < W - 1;
+    const float4 ta = corner[li][lj], tb = corner[li][lj + 1], tc = corner[li + 1][lj], td = corner[li + 1][lj + 1];
+    InvCell t = {{ta.x, ta.y, tb.x, tb.y, tc.x, tc.y, td.x, td.y}, ta.z, tb.z, tc.z, td.z, ta.w, tb.w, tc.w, td.w,
+                 FLT_MAX, -FLT_MAX, FLT_MAX, -FLT_MAX, (unsigned)((i0 + li) * (W - 1) + (j0 + lj))};
+    // the cell's widened box: empty for a lane without a cell
+    if (active) {
+        t.lox = fminf(fminf(t.c.ax, t.c.bx), fminf(t.c.cx, t.c.dx)) - TL_EPS;
+        t.hix = fmaxf(fmaxf(t.c.ax, t.c.bx), fmaxf(t.c.cx, t.c.dx)) + TL_EPS;
+        t.loy = fminf(fminf(t.c.ay, t.c.by), fminf(t.c.cy, t.c.dy)) - TL_EPS;
+        t.hiy = fmaxf(fmaxf(t.c.ay, t.c.by), fmaxf(t.c.cy, t.c.dy)) + TL_EPS;
+    }
+    int x0, x1, y0, y1;
+    ts_centre_range(t.lox, t.hix, W, x0, x1);
+    ts_centre_range(t.loy, t.hiy, H, y0, y1);
+    const int bw = max(x1 - x0 + 1, 0), bh = max(y1 - y0 + 1, 0);          // bw <= W, bh <= H: the product is at most H * W < 2^31
+    const int count = active ? bw * bh : 0;
+    // phase 1
+    const int n1 = count <= TI_INLINE ? count : 0;
+    for (int k = 0; k < n1; ++k) ts_invert_try(t, x0 + k % bw, y0 + k / bw, W, thr, keys);
+    // phase 2: `big` and everything read from lane b are wave-uniform
+    unsigned long long big = __ballot(count > TI_INLINE);
+    while (big) {
+        const int b = __ffsll((long long)big) - 1;
+        big &= big - 1;
+        const InvCell s = {{ts_lane_f(t.c.ax, b), ts_lane_f(t.c.ay, b), ts_lane_f(t.c.bx, b), ts_lane_f(t.c.by, b),
+                            ts_lane_f(t.c.cx, b), ts_lane_f(t.c.cy, b), ts_lane_f(t.c.dx, b), ts_lane_f(t.c.dy, b)},
+                           ts_lane_f(t.oa, b), ts_lane_f(t.ob, b), ts_lane_f(t.oc, b), ts_lane_f(t.od, b),
+                           ts_lane_f(t.sa, b), ts_lane_f(t.sb, b), ts_lane_f(t.sc, b), ts_lane_f(t.sd, b),
+                           ts_lane_f(t.lox, b), ts_lane_f(t.hix, b), ts_lane_f(t.loy, b), ts_lane_f(t.hiy, b),
+                           (unsigned)__builtin_amdgcn_readlane((int)t.cell, b)};
+        const int sx0 = __builtin_amdgcn_readlane(x0, b), sy0 = __builtin_amdgcn_readlane(y0, b);
+        const int sbw = __builtin_amdgcn_readlane(bw, b), scount = __builtin_amdgcn_readlane(count, b);
+        for (int k = lane; k < scount; k += 64) ts_invert_try(s, sx0 + k % sbw, sy0 + k / sbw, W, thr, keys);
+    }
+}
+
+// One lane per pixel of frame g (blockIdx.x = g * blocks + block): the query is the pixel's centre.
+__global__ __launch_bounds__(256) void ts_invert_resolve_kernel(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
+                                                                int blocks, int H, int W, const unsigned long long *__restrict__ keys,
+                                                                float *__restrict__ table, int *__restrict__ cell_out) {
+    const int g = blockIdx.x / blocks;
+    const int p = (blockIdx.x % blocks) * 256 + threadIdx.x;
+    if (p >= H * W) return;
+    const long long n = (long long)g * H * W + p;
+    float4 row;
+    const int cell = ts_resolve(frames, lohis, g, H, W, keys[n], (float)(p % W), (float)(p / W), row);
+    *reinterpret_cast<float4 *>(table + 4 * n) = row;
     cell_out[n] = cell;
 }
 
@@ -496,4 +611,35 @@ extern "C" int mftx_trackstore_locate(const uint16_t *const *frames, const float
     hipLaunchKernelGGL(ts_locate_resolve_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, reinterpret_cast<const uint2 *const *>(frames), lohis,
                        group_of, H, W, N, xy, keys, table, cell);
     return check_launch("trackstore_locate");
+}
+
+extern "C" int mftx_trackstore_invert(const uint16_t *const *frames, const float *const *lohis, int G, int H, int W,
+                                      float occlusion_threshold, unsigned long long *keys, float *table, int *cell, void *stream) {
+    if (G < 0) return fail(MFTX_E_ARG, "trackstore_invert: need G >= 0");
+    if (H < 2 || W < 2) return fail(MFTX_E_ARG, "trackstore_invert: H and W must be >= 2");
+    if (G == 0) return 0;
+    if (!frames || !lohis || !keys || !table || !cell) return fail(MFTX_E_ARG, "trackstore_invert: null pointer");
+    if ((long long)H * W > 0x7fffffffLL) return fail(MFTX_E_ARG, "trackstore_invert: more than 2^31 - 1 pixels (and cells)");
+    const int tiles_x = cdiv(W - 1, TL_TW), tiles_y = cdiv(H - 1, TL_TH);
+    const long long tiles = (long long)tiles_x * tiles_y, blocks = ((long long)H * W + 255) / 256;
+    if (tiles * G > 0x7fffffffLL || blocks * G > 0x7fffffffLL)
+        return fail(MFTX_E_ARG, "trackstore_invert: %lld cell tiles (%lld pixel blocks) x %d frames exceed one grid", tiles, blocks, G);
+    if (!aligned_to(frames, 8) || !aligned_to(lohis, 8) || !aligned_to(keys, 8))
+        return fail(MFTX_E_ALIGN, "trackstore_invert: the pointer tables and the keys must be 8-byte aligned");
+    if (!aligned_to(cell, 4)) return fail(MFTX_E_ALIGN, "trackstore_invert: cell must be 4-byte aligned");
+    if (!aligned16(table)) return fail(MFTX_E_ALIGN, "trackstore_invert: the table must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const long long n = (long long)G * H * W;
+    // per tile and frame: 33 x 9 packed corners; per pixel: its key set, (at least once) lowered and read, a row, a cell index, and
+    // the winning cell's four corners once more
+    ProfScope prof(PC_CHAIN, s, 8.0 * (TL_TW + 1) * (TL_TH + 1) * (double)tiles * G + (8.0 + 8.0 + 8.0 + 16.0 + 4.0 + 32.0) * (double)n);
+    hipError_t e = hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * (size_t)n, s);
+    if (e != hipSuccess) return fail((int)e, "trackstore_invert: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(ts_invert_scatter_kernel, dim3((unsigned)(tiles * G)), dim3(256), 0, s, reinterpret_cast<const uint2 *const *>(frames),
+                       lohis, tiles_x, (int)tiles, H, W, occlusion_threshold, keys);
+    int rc = check_launch("trackstore_invert");
+    if (rc) return rc;
+    hipLaunchKernelGGL(ts_invert_resolve_kernel, dim3((unsigned)(blocks * G)), dim3(256), 0, s, reinterpret_cast<const uint2 *const *>(frames),
+                       lohis, (int)blocks, H, W, keys, table, cell);
+    return check_launch("trackstore_invert");
 }

@@ -1082,6 +1082,42 @@ def trackstore_locate(chunks, lohi_chunks, point_slots, xy, table, cell, occlusi
     return table, cell
 
 
+def trackstore_invert(chunks, lohi_chunks, slots, table, cell, occlusion_threshold=0.5):
+    """Stored frames inverted densely, in one call (``mftx_trackstore_invert``): ``trackstore_locate`` with every pixel centre
+    (x, y) of the frame as a query, bit for bit, computed as a scatter from the template's cells.  chunks / lohi_chunks as for
+    ``trackstore_query``; slots: G HOST integers, the slots of the frames to invert (repeats welcome).  ``table`` (float32 device
+    [G,H,W,4]) receives per pixel the template point (x, y) whose image it is, and occlusion and sigma there; ``cell`` (int32
+    device [G,H,W]) the template cell, -1 (and a row of NaN) where nothing maps to the pixel.  The two pointer tables go up
+    through one pinned buffer; no host synchronisation.  Returns (table, cell)."""
+    lib = _lib.load()
+    chunks, lohi_chunks = list(chunks), list(lohi_chunks)
+    if not chunks or len(chunks) != len(lohi_chunks):
+        raise MftxError("trackstore_invert: as many lohi tables as chunks, at least one")
+    fpc, H, W = (int(s) for s in chunks[0].shape[:3])
+    for c, l in zip(chunks, lohi_chunks):
+        if tuple(c.shape) != (fpc, H, W, 4) or tuple(l.shape) != (fpc, 4, 2):
+            raise MftxError("trackstore_invert: chunks must be [frames_per_chunk,H,W,4] with lohi [frames_per_chunk,4,2]")
+    slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+    G = int(slots.shape[0])
+    if G and (slots.min() < 0 or slots.max() >= fpc * len(chunks)):
+        raise MftxError("trackstore_invert: slots must be slots of the store")
+    if tuple(table.shape) != (G, H, W, 4) or tuple(cell.shape) != (G, H, W):
+        raise MftxError("trackstore_invert: the table must be [G, H, W, 4], cell [G, H, W]")
+    cptr = np.asarray([_chk(c, "chunk", torch.uint16) for c in chunks], dtype=np.int64)
+    lptr = np.asarray([_chk(l, "lohi chunk") for l in lohi_chunks], dtype=np.int64)
+    tp, cp = _chk(table, "table"), _chk(cell, "cell", torch.int32)
+    if G == 0:
+        return table, cell
+    chunk, within = slots // fpc, slots % fpc
+    buf = np.concatenate([cptr[chunk] + within * (H * W * 8), lptr[chunk] + within * 32])
+    tables = torch.from_numpy(buf).pin_memory().to(table.device, non_blocking=True)
+    keys = torch.empty(G * H * W, dtype=torch.int64, device=table.device)
+    base = tables.data_ptr()
+    check(lib.mftx_trackstore_invert(base, base + 8 * G, G, H, W, float(occlusion_threshold), keys.data_ptr(), tp, cp, _stream()),
+          "mftx_trackstore_invert")
+    return table, cell
+
+
 class RaftEngine:
     """Handle on the native refinement runtime (``mftx_raft_*``)."""
 

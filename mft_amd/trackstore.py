@@ -15,6 +15,9 @@ flow that passes through its disk cache: half a quantisation step of each channe
     result = store.result(frame_i)                    # the dequantised FlowOUTrackingResult, on the device
     table, cell = store.locate(points_on_57, 57)      # the stored map inverted: template x, y, occlusion, sigma; cell -1 = none
     coords, occl, found = store.tracks_from(points_on_57, 57)     # ... and those template points followed over the frames
+    table, cell = store.inverse(57)                   # locate at EVERY pixel of frame 57: [H, W, 4], [H, W]
+    flow, occl, sigma, found = store.results_from(57) # dense results from frame 57 to every stored frame: [T, 2, H, W], ...
+    result, found = store.result_from(57, 80)         # ... one of them as a FlowOUTrackingResult
 
 ``device="cpu"`` is a host restatement of the same operations (numpy / torch), which pins the semantics without a GPU.
 """
@@ -109,7 +112,8 @@ def _locate_host(planes, q, thr, table, cell):
     for n in range(q.shape[0]):
         qx, qy = q[n, 0], q[n, 1]
         table[n], cell[n] = np.nan, -1
-        idx = np.flatnonzero((qx >= lox) & (qx <= hix) & (qy >= loy) & (qy <= hiy))       # the prefilter
+        idx = np.flatnonzero((qy >= loy) & (qy <= hiy))                                   # the prefilter: rows first, then
+        idx = idx[(qx >= lox[idx]) & (qx <= hix[idx])]                                    # columns among the cells that are left
         if idx.size == 0:
             continue
         u, v, ok = _solve_cells((ax[idx], ay[idx], bx[idx], by[idx], cx[idx], cy[idx], dx[idx], dy[idx]), qx, qy)
@@ -333,3 +337,81 @@ class DenseTrackStore:
         coords, occl = tracks[:, :, 0:2].copy(), tracks[:, :, 2].copy()
         coords[~found], occl[~found] = np.nan, 1.0
         return coords, occl, found
+
+    # ------------------------------------------------------------------ the dense inverse: every pixel of a stored frame
+    def _pixel_grid(self):
+        """float32 [H * W, 2] on the store's device: the pixel centres (x, y), row-major."""
+        idx = torch.arange(self.H * self.W, device=self.device)
+        return torch.stack([idx % self.W, torch.div(idx, self.W, rounding_mode="floor")], dim=1).to(torch.float32)
+
+    def inverse(self, frame, occlusion_threshold=0.5, out=None):
+        """Stored frame ``frame`` inverted at every pixel: ``locate`` with the H * W pixel centres as its points, bit for bit ->
+        (table [H, W, 4] float32, cell [H, W] int32) on the store's device: table[y, x] = (template x, template y, occlusion,
+        sigma) of the template point whose image is pixel (x, y) of that frame, cell[y, x] its template cell, -1 (and a row of
+        NaN) where nothing maps to the pixel.  A sequence of G frame ids gives [G, H, W, 4] and [G, H, W].  ``out``: a
+        (table, cell) pair to write into.  On the device: ONE call whatever G is -- every template cell writes itself onto the
+        pixels its image covers (csrc/trackstore.hip, ts_invert_scatter_kernel) -- and no host synchronisation."""
+        ids = np.asarray(frame)
+        if ids.ndim == 0:
+            slots, lead = [self.slot_of(ids)], ()              # KeyError for a frame that was never appended
+        elif ids.ndim == 1:
+            slots, lead = [self.slot_of(f) for f in ids], (int(ids.shape[0]),)
+        else:
+            raise ValueError("DenseTrackStore.inverse: frame must be one frame id or a sequence of them")
+        H, W = self.H, self.W
+        if out is None:
+            out = (torch.empty(lead + (H, W, 4), dtype=torch.float32, device=self.device),
+                   torch.empty(lead + (H, W), dtype=torch.int32, device=self.device))
+        table, cell = out
+        if tuple(table.shape) != lead + (H, W, 4) or table.dtype != torch.float32 or tuple(cell.shape) != lead + (H, W) \
+                or cell.dtype != torch.int32 or table.device.type != self.device.type or cell.device.type != self.device.type \
+                or not table.is_contiguous() or not cell.is_contiguous():
+            raise ValueError(f"DenseTrackStore.inverse: out must be contiguous (float32 {list(lead + (H, W, 4))}, int32 "
+                             f"{list(lead + (H, W))}) tensors on {self.device}")
+        G = len(slots)
+        if G == 0:
+            return table, cell
+        if self.native:
+            from . import ops
+            ops.trackstore_invert(self._chunks, self._lohi, slots, table.view(G, H, W, 4), cell.view(G, H, W), occlusion_threshold)
+        else:
+            grid = self._pixel_grid()
+            tb, cl = table.view(G, H * W, 4), cell.view(G, H * W)
+            for k, slot in enumerate(slots):
+                self.locate(grid, self.frame_ids[slot], occlusion_threshold, out=(tb[k], cl[k]))
+        return table, cell
+
+    def results_from(self, src, frames=None, occlusion_threshold=0.5):
+        """The dense results FROM stored frame ``src`` to ``frames`` (a sequence of stored frame ids; default: all, in append
+        order) -> (flow [T, 2, H, W], occlusion [T, 1, H, W], sigma [T, 1, H, W], found [H, W] bool) on the store's device.
+        Pixel p = (x, y) of ``src`` is taken back to its template point by ``inverse(src)`` -- (Px, Py, o_src, s_src) -- and that
+        point forward by ``query`` -- (qx, qy, o_dst, s_dst) on frame t: flow = (qx - x, qy - y), occlusion = max(o_src, o_dst),
+        sigma = sqrt(s_src^2 + s_dst^2), the rule by which results are chained (MFT/MFT.py:233-239) with the inverse as the left
+        result.  A pixel nothing maps to has found False, NaN flow, occlusion 1 and sigma +inf.  No host synchronisation."""
+        H, W = self.H, self.W
+        slots = self._slots(frames)                             # KeyError before any work
+        table, cell = self.inverse(src, occlusion_threshold)
+        table, found = table.view(H * W, 4), cell.view(H * W) >= 0
+        zero = torch.zeros((), dtype=torch.float32, device=self.device)
+        template = torch.where(found[:, None], table[:, 0:2], zero)
+        q = self.query(template, [self.frame_ids[s] for s in slots])                     # [H * W, T, 4]
+        T = int(q.shape[1])
+        flow = q[:, :, 0:2] - self._pixel_grid()[:, None, :]
+        occl = torch.maximum(table[:, None, 2], q[:, :, 2])
+        s_src, s_dst = table[:, None, 3], q[:, :, 3]
+        # (the root taken in float64 and rounded once: the correctly rounded float32 root on every device -- torch's own float32
+        # sqrt is an ulp off numpy's for some arguments on the host)
+        sigma = torch.sqrt((s_src * s_src + s_dst * s_dst).to(torch.float64)).to(torch.float32)
+        f = found[:, None]
+        flow = torch.where(f[:, :, None], flow, torch.full((), float("nan"), dtype=torch.float32, device=self.device))
+        occl = torch.where(f, occl, torch.ones((), dtype=torch.float32, device=self.device))
+        sigma = torch.where(f, sigma, torch.full((), float("inf"), dtype=torch.float32, device=self.device))
+        return (flow.permute(1, 2, 0).reshape(T, 2, H, W), occl.t().reshape(T, 1, H, W), sigma.t().reshape(T, 1, H, W),
+                found.view(H, W))
+
+    def result_from(self, src, dst, occlusion_threshold=0.5):
+        """-> (``FlowOUTrackingResult`` of the flow from stored frame ``src`` to stored frame ``dst``, found [H, W] bool): one
+        frame of ``results_from``, ready for ``warp_forward_device`` / ``warp_backward`` (mask the pixels that are not found:
+        their flow is NaN)."""
+        flow, occl, sigma, found = self.results_from(src, [dst], occlusion_threshold)
+        return FlowOUTrackingResult(flow[0], occl[0], sigma[0], validate=False), found
