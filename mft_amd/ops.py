@@ -1269,15 +1269,51 @@ class RaftEngine:
     #: regions stored in split form when the engine runs the split arithmetic (they feed GEMMs), and their row strides
     SPLIT_REGIONS = {"cor1": 256, "corflo": 256, "flo1": 128, "hx": 384, "rh": 128, "ouin": 712}
 
-    def region(self, name, P, h, w, cols):
+    def region(self, name, P, h, w, cols, split=None):
         """A workspace region as [P*h*w, cols] fp32 (parity tests): a view, or -- for the regions the split arithmetic
-        keeps in split form -- the decoded values."""
+        keeps in split form -- the decoded values.  split: None = decode SPLIT_REGIONS where ``plan(P, h, w)["presplit"]`` says
+        activations are kept in split form (with presplit = 0 they are fp32 like everything else); True / False = decode the
+        region's first ``cols`` columns as one row / do not, whatever the name (``fh``, below).  A region that is not decoded is
+        viewed with ``cols`` floats per cell, so ``cols`` must be its whole row there (``ou``: 4, ``hx``: 384).
+
+        What a region holds after ``refine`` returns (RefineCall::core; tests/refine_reference.py: REGION_MAP is this table, and
+        tests/test_gpu_refine_family.py holds every entry against fp64).  Last iteration = the one the call ended with.
+
+        ==========  =======  ==============================================================  ================================
+        region      columns  holds                                                           on which plans
+        ==========  =======  ==============================================================  ================================
+        lvl0..lvl3           the correlation pyramid (``pyramid_layout``)                    every plan but ``ondemand_corr``
+        corr        0:324    the lookup features the last iteration started from             every plan
+        cor1        0:256    relu(convc1), last iteration (split)                            every plan
+        corflo      0:256    relu(convc2) 0:192 | relu(convf2) 192:256, last iteration       every plan
+                             (split)
+        hx          0:128    h after the last vertical GRU pass (split)                      every plan
+        hx          128:256  the caller's inp (split: its split round trip)                  every plan
+        hx          256:384  motion features 0:126 | the flow they were formed from, x y     every plan
+                             (split)
+        delta       0:2      the last iteration's update                                     every plan
+        coords1     0:2      the coordinates after the last update                           every plan
+        fh          0:256    relu(mask.0) (split where presplit; not in SPLIT_REGIONS: until every plan
+                             the mask head runs it is the flow head's fp32 scratch)
+        mask        0:576    0.25 * mask.2(...)                                              every plan
+        ou          0:3      occlusion logits 0:2 | uncertainty 2 (column 3 unused)          every plan
+        flow_lr     0:2      coords1 - grid, unless ``refine(want_flow_lr=True)`` took it    every plan
+        flo1        0:128    relu(convf1), last iteration (split)                            plan["flow"] != "fused" (fused:
+                                                                                             the second coordinate buffer)
+        z, rh       0:128    the vertical pass's z gate; r * h (rh split)                    not plan["gru_fused"]
+        ouin        0:712    net | inp | corr | flow_lr | delta | motion (split)             plan["ou_materialised"]
+        ouh         0:256    relu(conv1) of the occlusion | uncertainty head                 not plan["ou_fused"] (fused: the
+                                                                                             projection's partial sums)
+        ==========  =======  ==============================================================  ================================
+        """
         offs = (C.c_size_t * 19)()
         check(_lib.load().mftx_raft_workspace_layout_for(self._h, P, h, w, offs, 19), "mftx_raft_workspace_layout_for")
         off = offs[self.REGIONS.index(name)]
         M = P * h * w
-        if self.arith == ARITH_SPLIT and name in self.SPLIT_REGIONS:
-            ld = self.SPLIT_REGIONS[name]
+        if split is None:
+            split = self.arith == ARITH_SPLIT and name in self.SPLIT_REGIONS and self.plan(P, h, w)["presplit"]
+        if split:
+            ld = self.SPLIT_REGIONS.get(name, cols)
             raw = self._ws[off: off + 4 * M * ld].view(torch.float32).reshape(M, ld)
             return unsplit_activations(raw)[:, :cols]
         return self._ws[off: off + 4 * M * cols].view(torch.float32).reshape(M, cols)

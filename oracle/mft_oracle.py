@@ -291,34 +291,48 @@ def _conv(x, sd, name, padding):
     return F.conv2d(x, sd[name + ".weight"], sd[name + ".bias"], padding=padding)
 
 
-def motion_encoder(sd, flow, corr):
+def motion_encoder(sd, flow, corr, rec=None):
+    """rec (optional dict): receives the stages a kernel materialises -- cor1 = relu(convc1), flo1 = relu(convf1), corflo = the input
+    of conv [relu(convc2) | relu(convf2)]."""
     e = "update_block.encoder"
-    cor = F.relu(_conv(corr, sd, e + ".convc1", 0))
-    cor = F.relu(_conv(cor, sd, e + ".convc2", 1))
-    flo = F.relu(_conv(flow, sd, e + ".convf1", 3))
-    flo = F.relu(_conv(flo, sd, e + ".convf2", 1))
-    out = F.relu(_conv(torch.cat([cor, flo], 1), sd, e + ".conv", 1))
+    cor1 = F.relu(_conv(corr, sd, e + ".convc1", 0))
+    cor = F.relu(_conv(cor1, sd, e + ".convc2", 1))
+    flo1 = F.relu(_conv(flow, sd, e + ".convf1", 3))
+    flo = F.relu(_conv(flo1, sd, e + ".convf2", 1))
+    corflo = torch.cat([cor, flo], 1)
+    out = F.relu(_conv(corflo, sd, e + ".conv", 1))
+    if rec is not None:
+        rec.update(cor1=cor1, flo1=flo1, corflo=corflo)
     return torch.cat([out, flow], 1)
 
 
-def sep_conv_gru(sd, h, x):
+def sep_conv_gru(sd, h, x, rec=None):
+    """rec (optional dict): receives h after the horizontal pass (h_horizontal) and the vertical pass's z gate and r * h (z, rh)."""
     g = "update_block.gru"
     for sfx, pad in (("1", (0, 2)), ("2", (2, 0))):
         hx = torch.cat([h, x], 1)
         z = torch.sigmoid(_conv(hx, sd, g + ".convz" + sfx, pad))
         r = torch.sigmoid(_conv(hx, sd, g + ".convr" + sfx, pad))
-        q = torch.tanh(_conv(torch.cat([r * h, x], 1), sd, g + ".convq" + sfx, pad))
+        rh = r * h
+        q = torch.tanh(_conv(torch.cat([rh, x], 1), sd, g + ".convq" + sfx, pad))
         h = (1 - z) * h + z * q
+        if rec is not None:
+            rec.update({"h_horizontal": h} if sfx == "1" else {"z": z, "rh": rh})
     return h
 
 
-def update_block(sd, net, inp, corr, flow):
-    """-> net, up_mask, delta_flow, motion_features (core/update.py:229-238)."""
-    motion = motion_encoder(sd, flow, corr)
-    net = sep_conv_gru(sd, net, torch.cat([inp, motion], 1))
+def update_block(sd, net, inp, corr, flow, rec=None):
+    """-> net, up_mask, delta_flow, motion_features (core/update.py:229-238).  rec (optional dict): the stages in between, see
+    motion_encoder and sep_conv_gru, and the hidden layers of the two heads (flow_hidden, mask_hidden)."""
+    motion = motion_encoder(sd, flow, corr, rec)
+    net = sep_conv_gru(sd, net, torch.cat([inp, motion], 1), rec)
     u = "update_block"
-    delta = _conv(F.relu(_conv(net, sd, u + ".flow_head.conv1", 1)), sd, u + ".flow_head.conv2", 1)
-    mask = 0.25 * _conv(F.relu(_conv(net, sd, u + ".mask.0", 1)), sd, u + ".mask.2", 0)
+    flow_hidden = F.relu(_conv(net, sd, u + ".flow_head.conv1", 1))
+    delta = _conv(flow_hidden, sd, u + ".flow_head.conv2", 1)
+    mask_hidden = F.relu(_conv(net, sd, u + ".mask.0", 1))
+    mask = 0.25 * _conv(mask_hidden, sd, u + ".mask.2", 0)
+    if rec is not None:
+        rec.update(flow_hidden=flow_hidden, mask_hidden=mask_hidden)
     return net, mask, delta, motion
 
 
@@ -326,12 +340,16 @@ def update_block(sd, net, inp, corr, flow):
 # a11: occlusion + uncertainty heads (core/update.py:17-75,196-214)
 # ---------------------------------------------------------------------------
 
-def ou_block(sd, net, inp, corr, flow, delta_flow, motion):
+def ou_block(sd, net, inp, corr, flow, delta_flow, motion, rec=None):
+    """rec (optional dict): receives the 712-channel input (ou_input) and the two hidden layers (ou_hidden: occlusion | uncertainty)."""
     x = torch.cat([net, inp, corr, flow, delta_flow, motion], 1)   # 712 channels
     o = "occlusion_block"
-    occl = _conv(F.relu(_conv(x, sd, o + ".occl_head.conv1", 1)), sd, o + ".occl_head.conv2", 1)
-    unc = _conv(F.relu(_conv(x, sd, o + ".uncertainty_head.conv1", 1)), sd,
-                o + ".uncertainty_head.conv2", 1)
+    ho = F.relu(_conv(x, sd, o + ".occl_head.conv1", 1))
+    hu = F.relu(_conv(x, sd, o + ".uncertainty_head.conv1", 1))
+    occl = _conv(ho, sd, o + ".occl_head.conv2", 1)
+    unc = _conv(hu, sd, o + ".uncertainty_head.conv2", 1)
+    if rec is not None:
+        rec.update(ou_input=x, ou_hidden=torch.cat([ho, hu], 1))
     return occl, unc
 
 
@@ -375,7 +393,12 @@ class _Stage:
 
 
 def raft_refine(sd, fmap1, fmap2, net, inp, iters, flow_init=None, trace=None, timers=None):
-    """The iterative part of RAFT.forward, from feature maps onwards."""
+    """The iterative part of RAFT.forward, from feature maps onwards.
+
+    trace (optional list): receives one dict per iteration with every stage a kernel materialises -- corr (the 324 lookup features),
+    cor1, flo1, corflo, motion (126 + flow), h_horizontal, z, rh, net (h after the vertical pass), flow_hidden, mask_hidden, delta,
+    coords1 (after the update) -- and, in the last iteration's dict, what is formed after the loop: mask (with its 0.25), ou_input,
+    ou_hidden, occl and unc (the logits at 1/8 resolution), flow_lr."""
     _, _, h, w = fmap1.shape
     with _Stage(timers, "corr_volume_pyramid"):
         pyr = corr_pyramid(corr_volume(fmap1, fmap2))
@@ -387,14 +410,19 @@ def raft_refine(sd, fmap1, fmap2, net, inp, iters, flow_init=None, trace=None, t
         with _Stage(timers, "corr_lookup"):
             corr = corr_lookup(pyr, coords1)
         flow = coords1 - coords0
+        rec = {} if trace is not None else None
         with _Stage(timers, "update_block"):
-            net, mask, delta, motion = update_block(sd, net, inp, corr, flow)
+            net, mask, delta, motion = update_block(sd, net, inp, corr, flow, rec)
         coords1 = coords1 + delta
         if trace is not None:
-            trace.append(dict(corr=corr, net=net, delta=delta, coords1=coords1))
+            rec.update(corr=corr, motion=motion, net=net, delta=delta, coords1=coords1)
+            trace.append(rec)
     flow_lr = coords1 - coords0
+    rec = trace[-1] if trace else None
     with _Stage(timers, "ou_block"):
-        occl, unc = ou_block(sd, net, inp, corr, flow_lr, delta, motion)
+        occl, unc = ou_block(sd, net, inp, corr, flow_lr, delta, motion, rec)
+    if rec is not None:
+        rec.update(mask=mask, occl=occl, unc=unc, flow_lr=flow_lr)
     with _Stage(timers, "convex_upsample"):
         return dict(flow=convex_upsample(flow_lr, mask, 8.0),
                     occlusion=convex_upsample(occl, mask, 1.0),
