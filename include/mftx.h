@@ -604,6 +604,18 @@ size_t mftx_trackstore_workspace_bytes(void);
 int mftx_trackstore_append(const float *flow, const float *occl, const float *sigma, int H, int W,
                            uint16_t *packed, float *lohi, void *workspace, size_t workspace_bytes, void *stream);
 
+/* T results quantised in one call -- what a multi-template pass appends per video frame.  flow, occl, sigma, packed and lohi are
+ * HOST arrays of T device pointers (frame j: flow[j] [2][H][W], occl[j] / sigma[j] [1][H][W], packed[j], lohi[j] as above, the
+ * same alignments).  The descriptors travel in the kernel arguments, 64 frames per argument block (under 4 KB): two launches
+ * per 64 frames, frame j = blockIdx.y, no allocation, no copy, no synchronisation.  Frame j's packed words and lohi are bitwise
+ * what mftx_trackstore_append gives for that frame alone (min and max do not depend on the order they are taken in; the
+ * quantisation is per pixel).  workspace: mftx_trackstore_append_multi_workspace_bytes(T) bytes of device memory -- the
+ * partials [T][blocks][4][2].  T == 0: nothing is done, 0 is returned. */
+size_t mftx_trackstore_append_multi_workspace_bytes(int T);
+int mftx_trackstore_append_multi(int T, const float *const *flow, const float *const *occl, const float *const *sigma,
+                                 int H, int W, uint16_t *const *packed, float *const *lohi,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+
 /* One stored frame back to planes: per channel bitwise mftx_dequantize_u16 with that channel's (lo, hi), which are read
  * from device memory here (no host round trip).  For forward warps / overlays after the fact, and for export. */
 int mftx_trackstore_unpack(const uint16_t *packed, const float *lohi, int H, int W,
@@ -664,6 +676,24 @@ int mftx_trackstore_locate(const uint16_t *const *frames, const float *const *lo
 int mftx_trackstore_invert(const uint16_t *const *frames, const float *const *lohis, int G, int H, int W,
                            float occlusion_threshold, unsigned long long *keys /* [G*H*W] */,
                            float *table, int *cell, void *stream);
+
+/* Stored frames of SEVERAL stores (the entries of a track atlas, mft_amd/trackatlas.py) inverted densely onto one plane per video
+ * frame.  J stored frames, G planes; all tables are DEVICE memory, as for mftx_trackstore_invert:
+ *   frames [J] / lohis [J]: the stored frames, those of plane g being j = first_of[g] .. first_of[g + 1] - 1 in ascending rank;
+ *   first_of [G + 1] int32 (ascending, first_of[0] = 0, first_of[G] = J); rank_of [J] int32: what `entry` reports for frame j.
+ * Every cell of frame j = first_of[g] + k writes its key onto the pixel centres of plane g that its widened box holds, exactly as
+ * mftx_trackstore_invert scatters; the key is bit 63 = occluded, bits 62..32 = the bits of sigma, bits 31..24 = k, bits 23..0 =
+ * the cell.  Its minimum is the per-entry mftx_trackstore_invert followed by the smallest (occluded, sigma, k) over the
+ * entries that found the pixel, bit for bit; the resolve step solves the winning cell of frame first_of[g] + k again.
+ *   keys [G * H * W] 64-bit words: workspace; table [G][H][W][4], cell [G][H][W] as for mftx_trackstore_invert (the winner's);
+ *   entry [G][H][W] int32: rank_of[first_of[g] + k] of the winner, -1 (with cell -1 and four NaNs) where no entry finds the pixel.
+ * A plane without entries is all "not found".  MFTX_E_ARG: more than 2^24 cells ((H - 1)(W - 1)), or J > 256 G (some plane has
+ * more than 256 entries -- the tables themselves are device memory and are not read here: of a plane that lists more than 256,
+ * the entries beyond are left out).  One memset and two launches whatever G and J are; no allocation, no synchronisation.
+ * G == 0: nothing is done, 0 is returned. */
+int mftx_trackstore_invert_atlas(const uint16_t *const *frames, const float *const *lohis, const int *first_of /* [G+1] */,
+                                 const int *rank_of /* [J] */, int G, int J, int H, int W, float occlusion_threshold,
+                                 unsigned long long *keys /* [G*H*W] */, float *table, int *cell, int *entry, void *stream);
 
 /* ---- 8f-4: frame / result transport without copy queues -------------------------------------------------------------------
  * A copy KERNEL: src -> dst, n bytes, both 16-byte aligned; either may be PINNED HOST memory (hipHostMalloc / torch

@@ -49,6 +49,9 @@ def __getattr__(name):  # lazy: these import torch-heavy modules
     if name == "MultiTemplateMFT":
         from .multi import MultiTemplateMFT
         return MultiTemplateMFT
+    if name == "TrackAtlas":
+        from .trackatlas import TrackAtlas
+        return TrackAtlas
     if name == "RAFTWrapper":
         from .raft import RAFTWrapper
         return RAFTWrapper

@@ -139,6 +139,11 @@ SIGNATURES = {
     "mftx_trackstore_workspace_bytes": (C.c_size_t, []),
     "mftx_trackstore_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mftx_trackstore_append_multi_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "mftx_trackstore_append_multi": (C.c_int, [C.c_int, _PP, _PP, _PP, C.c_int, C.c_int, _PP, _PP, C.c_void_p, C.c_size_t,
+                                               C.c_void_p]),
+    "mftx_trackstore_invert_atlas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mftx_trackstore_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
     "mftx_trackstore_query": (C.c_int, [_PP, _PP, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,

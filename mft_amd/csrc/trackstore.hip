@@ -48,8 +48,7 @@ __device__ __forceinline__ void ts_block_minmax(float &lo, float &hi, float *sh 
 }
 
 // partial: [gridDim.x][4][2] = (min, max) of each channel over the block's pixels
-__global__ __launch_bounds__(TS_T) void ts_minmax_kernel(Frame4 f, long long n, float *__restrict__ partial) {
-    __shared__ float sh[2 * TS_T / 64];
+__device__ __forceinline__ void ts_minmax_body(const Frame4 &f, long long n, float *__restrict__ partial, float *sh) {
     float lo[4], hi[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) { lo[c] = FLT_MAX; hi[c] = -FLT_MAX; }
@@ -85,9 +84,13 @@ __global__ __launch_bounds__(TS_T) void ts_minmax_kernel(Frame4 f, long long n, 
     }
 }
 
-__global__ __launch_bounds__(TS_T) void ts_pack_kernel(Frame4 f, long long n, const float *__restrict__ partial, int n_partial,
-                                                       ushort4 *__restrict__ packed, float *__restrict__ lohi) {
+__global__ __launch_bounds__(TS_T) void ts_minmax_kernel(Frame4 f, long long n, float *__restrict__ partial) {
     __shared__ float sh[2 * TS_T / 64];
+    ts_minmax_body(f, n, partial, sh);
+}
+
+__device__ __forceinline__ void ts_pack_body(const Frame4 &f, long long n, const float *__restrict__ partial, int n_partial,
+                                             ushort4 *__restrict__ packed, float *__restrict__ lohi, float *sh) {
     float lo[4], range[4];
     bool flat[4];
 #pragma unroll
@@ -123,6 +126,34 @@ __global__ __launch_bounds__(TS_T) void ts_pack_kernel(Frame4 f, long long n, co
     }
     for (; i < n; i += stride)
         packed[i] = make_ushort4(enc(0, f.p[0][i]), enc(1, f.p[1][i]), enc(2, f.p[2][i]), enc(3, f.p[3][i]));
+}
+
+__global__ __launch_bounds__(TS_T) void ts_pack_kernel(Frame4 f, long long n, const float *__restrict__ partial, int n_partial,
+                                                       ushort4 *__restrict__ packed, float *__restrict__ lohi) {
+    __shared__ float sh[2 * TS_T / 64];
+    ts_pack_body(f, n, partial, n_partial, packed, lohi, sh);
+}
+
+// append_multi: the two kernels above for up to TSM_F frames per launch, frame j = blockIdx.y.  The frames' descriptors travel in
+// the kernel arguments (as chain.hip's MultiSet does); frame j's partials are rows j * gridDim.x .. of the workspace, and its
+// blocks do exactly what the single-frame kernels' blocks do: the same bits.
+constexpr int TSM_F = 64;           // frames per launch: 64 x 48 B = 3072 B of kernel arguments
+struct MultiFrame { const float *p[4]; ushort4 *packed; float *lohi; };
+struct MultiFrameSet { MultiFrame f[TSM_F]; };
+static_assert(sizeof(MultiFrameSet) + 64 <= 4096, "kernel arguments of the append_multi kernels exceed 4 KB");
+
+__global__ __launch_bounds__(TS_T) void ts_minmax_multi_kernel(MultiFrameSet fs, long long n, float *__restrict__ partial) {
+    __shared__ float sh[2 * TS_T / 64];
+    const MultiFrame &m = fs.f[blockIdx.y];
+    const Frame4 f{{m.p[0], m.p[1], m.p[2], m.p[3]}};
+    ts_minmax_body(f, n, partial + 8 * (long long)blockIdx.y * gridDim.x, sh);
+}
+
+__global__ __launch_bounds__(TS_T) void ts_pack_multi_kernel(MultiFrameSet fs, long long n, const float *__restrict__ partial) {
+    __shared__ float sh[2 * TS_T / 64];
+    const MultiFrame &m = fs.f[blockIdx.y];
+    const Frame4 f{{m.p[0], m.p[1], m.p[2], m.p[3]}};
+    ts_pack_body(f, n, partial + 8 * (long long)blockIdx.y * gridDim.x, (int)gridDim.x, m.packed, m.lohi, sh);
 }
 
 // dequantize_kernel's dec() for the four channels of one packed pixel
@@ -428,15 +459,13 @@ __device__ __forceinline__ void ts_invert_try(const InvCell &t, int x, int y, in
 // Grid: cell tiles x frames (blockIdx.x = g * tiles + tile), a cell per lane, the tile's corners staged as the search kernel
 // stages them.  Phase 1: a lane whose range holds at most TI_INLINE centres walks it.  Phase 2: the wave takes the larger cells
 // one at a time, its 64 lanes striding over the range, so that a torn cell's frame-sized box costs area / 64 solves per lane.
-__global__ __launch_bounds__(256) void ts_invert_scatter_kernel(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
-                                                                int tiles_x, int tiles, int H, int W, float thr,
-                                                                unsigned long long *__restrict__ keys) {
-    __shared__ float4 corner[TL_TH + 1][TL_TW + 1];       // (M x, M y, occlusion, sigma) of the tile's corners
-    const int g = blockIdx.x / tiles, tile = blockIdx.x % tiles;
+// `keys` is the key plane of the frame; `key_hi` is OR-ed onto the cell in the key's low word (the atlas puts an entry's index there).
+__device__ __forceinline__ void ts_invert_scatter_body(const uint2 *__restrict__ frame, const float *__restrict__ lohi, int tile,
+                                                       int tiles_x, int H, int W, float thr, unsigned long long *__restrict__ keys,
+                                                       unsigned key_hi, float4 (*corner)[TL_TW + 1]) {
     const int i0 = (tile / tiles_x) * TL_TH, j0 = (tile % tiles_x) * TL_TW;
-    const uint2 *__restrict__ frame = frames[g];
     const int lane = threadIdx.x & 63;
-    const Dec4 dec(lohis[g]);
+    const Dec4 dec(lohi);
     for (int e = threadIdx.x; e < (TL_TH + 1) * (TL_TW + 1); e += 256) {
         const int ci = e / (TL_TW + 1), cj = e % (TL_TW + 1);
         const int i = min(i0 + ci, H - 1), j = min(j0 + cj, W - 1);           // (a ragged tile's cells beyond the frame are never used)
@@ -444,12 +473,11 @@ __global__ __launch_bounds__(256) void ts_invert_scatter_kernel(const uint2 *con
         corner[ci][cj] = make_float4((float)j + t.x, (float)i + t.y, t.z, t.w);
     }
     __syncthreads();
-    keys += (long long)g * H * W;
     const int li = threadIdx.x / TL_TW, lj = threadIdx.x % TL_TW;
     const bool active = i0 + li < H - 1 && j0 + lj < W - 1;
     const float4 ta = corner[li][lj], tb = corner[li][lj + 1], tc = corner[li + 1][lj], td = corner[li + 1][lj + 1];
     InvCell t = {{ta.x, ta.y, tb.x, tb.y, tc.x, tc.y, td.x, td.y}, ta.z, tb.z, tc.z, td.z, ta.w, tb.w, tc.w, td.w,
-                 FLT_MAX, -FLT_MAX, FLT_MAX, -FLT_MAX, (unsigned)((i0 + li) * (W - 1) + (j0 + lj))};
+                 FLT_MAX, -FLT_MAX, FLT_MAX, -FLT_MAX, key_hi | (unsigned)((i0 + li) * (W - 1) + (j0 + lj))};
     // the cell's widened box: empty for a lane without a cell
     if (active) {
         t.lox = fminf(fminf(t.c.ax, t.c.bx), fminf(t.c.cx, t.c.dx)) - TL_EPS;
@@ -482,6 +510,14 @@ __global__ __launch_bounds__(256) void ts_invert_scatter_kernel(const uint2 *con
     }
 }
 
+__global__ __launch_bounds__(256) void ts_invert_scatter_kernel(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
+                                                                int tiles_x, int tiles, int H, int W, float thr,
+                                                                unsigned long long *__restrict__ keys) {
+    __shared__ float4 corner[TL_TH + 1][TL_TW + 1];       // (M x, M y, occlusion, sigma) of the tile's corners
+    const int g = blockIdx.x / tiles, tile = blockIdx.x % tiles;
+    ts_invert_scatter_body(frames[g], lohis[g], tile, tiles_x, H, W, thr, keys + (long long)g * H * W, 0u, corner);
+}
+
 // One lane per pixel of frame g (blockIdx.x = g * blocks + block): the query is the pixel's centre.
 __global__ __launch_bounds__(256) void ts_invert_resolve_kernel(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
                                                                 int blocks, int H, int W, const unsigned long long *__restrict__ keys,
@@ -494,6 +530,54 @@ __global__ __launch_bounds__(256) void ts_invert_resolve_kernel(const uint2 *con
     const int cell = ts_resolve(frames, lohis, g, H, W, keys[n], (float)(p % W), (float)(p / W), row);
     *reinterpret_cast<float4 *>(table + 4 * n) = row;
     cell_out[n] = cell;
+}
+
+// ---- invert_atlas: several stored frames (the entries of a track atlas that hold one video frame) scattered onto ONE key plane ------
+// Plane g is built from the stored frames j = first_of[g] .. first_of[g + 1] - 1, listed in ascending rank.  Entry k = j - first_of[g]
+// goes into bits 31..24 of the key's low word, above the 24 bits of the cell: the minimum is locate's (occluded, sigma, cell) with
+// the rank put between sigma and cell, i.e. per-entry invert followed by the minimum of (occluded, sigma, rank) over the entries.
+constexpr int TA_ENTRIES = 256;                 // entries per plane (8 bits of the key)
+constexpr long long TA_CELLS = 1ll << 24;       // cells per frame (24 bits of the key)
+
+// Grid: cell tiles x stored frames (blockIdx.x = j * tiles + tile).  The plane of frame j is the last g with first_of[g] <= j.
+__global__ __launch_bounds__(256) void ts_atlas_scatter_kernel(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
+                                                               const int *__restrict__ first_of, int G, int tiles_x, int tiles, int H, int W,
+                                                               float thr, unsigned long long *__restrict__ keys) {
+    __shared__ float4 corner[TL_TH + 1][TL_TW + 1];
+    const int j = blockIdx.x / tiles, tile = blockIdx.x % tiles;
+    int g = 0, hi = G - 1;
+    while (g < hi) {
+        const int mid = (g + hi + 1) >> 1;
+        if (first_of[mid] <= j) g = mid; else hi = mid - 1;
+    }
+    const int k = j - first_of[g];
+    if (k < 0 || k >= TA_ENTRIES || j >= first_of[g + 1]) return;        // (block-uniform: a table that is not what it should be writes nothing)
+    ts_invert_scatter_body(frames[j], lohis[j], tile, tiles_x, H, W, thr, keys + (long long)g * H * W, (unsigned)k << 24, corner);
+}
+
+// One lane per pixel of plane g (blockIdx.x = g * blocks + block): the winning entry's cell solved again, as ts_invert_resolve_kernel does.
+__global__ __launch_bounds__(256) void ts_atlas_resolve_kernel(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
+                                                               const int *__restrict__ first_of, const int *__restrict__ rank_of, int blocks,
+                                                               int H, int W, const unsigned long long *__restrict__ keys,
+                                                               float *__restrict__ table, int *__restrict__ cell_out, int *__restrict__ entry_out) {
+    const int g = blockIdx.x / blocks;
+    const int p = (blockIdx.x % blocks) * 256 + threadIdx.x;
+    if (p >= H * W) return;
+    const long long n = (long long)g * H * W + p;
+    const unsigned long long key = keys[n];
+    const float nan = __uint_as_float(0x7fc00000u);
+    float4 row = make_float4(nan, nan, nan, nan);
+    int cell = -1, entry = -1;
+    if (key != TL_NONE) {
+        const int j = first_of[g] + (int)((key >> 24) & 0xffu);
+        if (j < first_of[g + 1]) {
+            cell = ts_resolve(frames, lohis, j, H, W, (key & ~0xffffffffull) | (key & 0xffffffull), (float)(p % W), (float)(p / W), row);
+            if (cell >= 0) entry = rank_of[j];
+        }
+    }
+    *reinterpret_cast<float4 *>(table + 4 * n) = row;
+    cell_out[n] = cell;
+    entry_out[n] = entry;
 }
 
 static int ts_blocks(long long n) {
@@ -526,6 +610,45 @@ extern "C" int mftx_trackstore_append(const float *flow, const float *occl, cons
     hipLaunchKernelGGL(ts_minmax_kernel, dim3(nb), dim3(TS_T), 0, s, f, n, partial);
     hipLaunchKernelGGL(ts_pack_kernel, dim3(nb), dim3(TS_T), 0, s, f, n, partial, nb, reinterpret_cast<ushort4 *>(packed), lohi);
     return check_launch("trackstore_append");
+}
+
+extern "C" size_t mftx_trackstore_append_multi_workspace_bytes(int T) {
+    return T > 0 ? (size_t)T * mftx_trackstore_workspace_bytes() : 0;
+}
+
+extern "C" int mftx_trackstore_append_multi(int T, const float *const *flow, const float *const *occl, const float *const *sigma,
+                                            int H, int W, uint16_t *const *packed, float *const *lohi, void *workspace,
+                                            size_t workspace_bytes, void *stream) {
+    if (T < 0) return fail(MFTX_E_ARG, "trackstore_append_multi: need T >= 0");
+    if (H < 2 || W < 2) return fail(MFTX_E_ARG, "trackstore_append_multi: H and W must be >= 2");
+    if (T == 0) return 0;
+    if (!flow || !occl || !sigma || !packed || !lohi || !workspace) return fail(MFTX_E_ARG, "trackstore_append_multi: null pointer");
+    for (int j = 0; j < T; ++j) {
+        if (!flow[j] || !occl[j] || !sigma[j] || !packed[j] || !lohi[j]) return fail(MFTX_E_ARG, "trackstore_append_multi: null pointer of frame %d", j);
+        if (!aligned_to(flow[j], 4) || !aligned_to(occl[j], 4) || !aligned_to(sigma[j], 4) || !aligned_to(lohi[j], 4))
+            return fail(MFTX_E_ALIGN, "trackstore_append_multi: planes and lohi of frame %d must be 4-byte aligned", j);
+        if (!aligned_to(packed[j], 8)) return fail(MFTX_E_ALIGN, "trackstore_append_multi: packed of frame %d must be 8-byte aligned", j);
+    }
+    if (!aligned_to(workspace, 4)) return fail(MFTX_E_ALIGN, "trackstore_append_multi: workspace must be 4-byte aligned");
+    if (workspace_bytes < mftx_trackstore_append_multi_workspace_bytes(T))
+        return fail(MFTX_E_WORKSPACE, "trackstore_append_multi: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const long long n = (long long)H * W;
+    const int nb = ts_blocks(n);
+    ProfScope prof(PC_GLUE, s, 40.0 * (double)n * T);
+    for (int j0 = 0; j0 < T; j0 += TSM_F) {
+        const int nf = T - j0 < TSM_F ? T - j0 : TSM_F;
+        MultiFrameSet fs = {};
+        for (int j = 0; j < nf; ++j)
+            fs.f[j] = MultiFrame{{flow[j0 + j], flow[j0 + j] + n, occl[j0 + j], sigma[j0 + j]},
+                                 reinterpret_cast<ushort4 *>(packed[j0 + j]), lohi[j0 + j]};
+        float *partial = (float *)workspace + 8 * (long long)j0 * TS_B_MAX;         // (frame j0 + j: rows j * nb .. of this launch's part)
+        hipLaunchKernelGGL(ts_minmax_multi_kernel, dim3(nb, nf), dim3(TS_T), 0, s, fs, n, partial);
+        hipLaunchKernelGGL(ts_pack_multi_kernel, dim3(nb, nf), dim3(TS_T), 0, s, fs, n, partial);
+        const int rc = check_launch("trackstore_append_multi");
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 extern "C" int mftx_trackstore_unpack(const uint16_t *packed, const float *lohi, int H, int W, float *flow, float *occl,
@@ -642,4 +765,44 @@ extern "C" int mftx_trackstore_invert(const uint16_t *const *frames, const float
     hipLaunchKernelGGL(ts_invert_resolve_kernel, dim3((unsigned)(blocks * G)), dim3(256), 0, s, reinterpret_cast<const uint2 *const *>(frames),
                        lohis, (int)blocks, H, W, keys, table, cell);
     return check_launch("trackstore_invert");
+}
+
+extern "C" int mftx_trackstore_invert_atlas(const uint16_t *const *frames, const float *const *lohis, const int *first_of,
+                                            const int *rank_of, int G, int J, int H, int W, float occlusion_threshold,
+                                            unsigned long long *keys, float *table, int *cell, int *entry, void *stream) {
+    if (G < 0 || J < 0) return fail(MFTX_E_ARG, "trackstore_invert_atlas: need G >= 0, J >= 0");
+    if (H < 2 || W < 2) return fail(MFTX_E_ARG, "trackstore_invert_atlas: H and W must be >= 2");
+    if ((long long)(H - 1) * (W - 1) > TA_CELLS) return fail(MFTX_E_ARG, "trackstore_invert_atlas: more than 2^24 cells");
+    if ((long long)J > (long long)TA_ENTRIES * G)
+        return fail(MFTX_E_ARG, "trackstore_invert_atlas: %d stored frames in %d planes: more than %d entries in a plane", J, G, TA_ENTRIES);
+    if (G == 0) return 0;
+    if (!first_of || !keys || !table || !cell || !entry || (J > 0 && (!frames || !lohis || !rank_of)))
+        return fail(MFTX_E_ARG, "trackstore_invert_atlas: null pointer");
+    const int tiles_x = cdiv(W - 1, TL_TW), tiles_y = cdiv(H - 1, TL_TH);
+    const long long tiles = (long long)tiles_x * tiles_y, blocks = ((long long)H * W + 255) / 256;
+    if (tiles * J > 0x7fffffffLL || blocks * G > 0x7fffffffLL)
+        return fail(MFTX_E_ARG, "trackstore_invert_atlas: %lld cell tiles x %d frames (%lld pixel blocks x %d planes) exceed one grid", tiles, J,
+                    blocks, G);
+    if (!aligned_to(frames, 8) || !aligned_to(lohis, 8) || !aligned_to(keys, 8))
+        return fail(MFTX_E_ALIGN, "trackstore_invert_atlas: the pointer tables and the keys must be 8-byte aligned");
+    if (!aligned_to(first_of, 4) || !aligned_to(rank_of, 4) || !aligned_to(cell, 4) || !aligned_to(entry, 4))
+        return fail(MFTX_E_ALIGN, "trackstore_invert_atlas: first_of, rank_of, cell and entry must be 4-byte aligned");
+    if (!aligned16(table)) return fail(MFTX_E_ALIGN, "trackstore_invert_atlas: the table must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const long long n = (long long)G * H * W;
+    // per tile and stored frame: 33 x 9 packed corners; per pixel of a plane: its key set and read, a row, a cell, an entry, the
+    // winning cell's four corners once more; per pixel of a stored frame: (at least) one key lowered
+    ProfScope prof(PC_CHAIN, s, 8.0 * (TL_TW + 1) * (TL_TH + 1) * (double)tiles * J + (8.0 + 8.0 + 16.0 + 4.0 + 4.0 + 32.0) * (double)n +
+                                    8.0 * (double)J * H * W);
+    hipError_t e = hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * (size_t)n, s);
+    if (e != hipSuccess) return fail((int)e, "trackstore_invert_atlas: %s", hipGetErrorString(e));
+    if (J > 0) {
+        hipLaunchKernelGGL(ts_atlas_scatter_kernel, dim3((unsigned)(tiles * J)), dim3(256), 0, s, reinterpret_cast<const uint2 *const *>(frames),
+                           lohis, first_of, G, tiles_x, (int)tiles, H, W, occlusion_threshold, keys);
+        const int rc = check_launch("trackstore_invert_atlas");
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(ts_atlas_resolve_kernel, dim3((unsigned)(blocks * G)), dim3(256), 0, s, reinterpret_cast<const uint2 *const *>(frames),
+                       lohis, first_of, rank_of, (int)blocks, H, W, keys, table, cell, entry);
+    return check_launch("trackstore_invert_atlas");
 }

@@ -92,6 +92,12 @@ class MultiTemplateMFT(MFT):
     templates.  ``max_templates`` (argument, else ``C.multi_template_max``, else 32) bounds a pass: ``init`` raises
     ``ValueError`` beyond it, and the caller runs more start frames in several passes (``tapvid.run_sequence_multi`` does).
 
+    ``C.multi_template_stores`` keeps a ``DenseTrackStore`` per template (``track_stores[start]``, 8 bytes per pixel and frame):
+    the store an ``MFT`` with ``C.track_store`` on that start frame alone would hold, word for word, filled by one
+    ``trackstore_append_multi`` call per frame.  ``C.track_store_frames_per_chunk`` applies per store,
+    ``C.track_store_max_bytes`` to their sum.  ``TrackAtlas.from_passes`` (mft_amd/trackatlas.py) joins the stores of a
+    forward and a backward pass.  ``C.track_store`` itself stays refused (it names the single tracker's one store).
+
     Not supported, and refused rather than ignored: ``C.delta_sharding`` (a multi-GPU pass) and a flow cache -- within one
     pass no pair is requested twice, so a cache would have nothing to return.
 
@@ -147,8 +153,9 @@ class MultiTemplateMFT(MFT):
         self._order = starts
         self._imgs = {}
         self._window_ids = set()
-        self.stats = dict(frames=0, pairs=0, engine_calls=0, chain_launches=0, readout_launches=0)
+        self.stats = dict(frames=0, pairs=0, engine_calls=0, chain_launches=0, readout_launches=0, store_append_calls=0)
         self._native = hasattr(self.backend, "chain_select_multi")
+        self.track_stores = {}                    # C.multi_template_stores: {start_frame: DenseTrackStore}, made as the templates start
         self._table = self._q_tmpl = self._q_xy = None
         self._host_tracks = {}
         self.n_frames = None
@@ -229,6 +236,10 @@ class MultiTemplateMFT(MFT):
             self.stats["chain_launches"] += len(running)
         # the guard runs before any bookkeeping changes (MFT._finish_frame); never a host wait here
         self._check_nonfinite(synced=False)
+        identity = FlowOUTrackingResult.identity((H, W), device=self.device) if starting is not None else None
+        if self.C.multi_template_stores:           # ... and so do the stores: a MemoryError leaves the pass as it was
+            self._append_stores(frame_i, [(t.start_frame_i, sel[:3]) for t, sel in zip(running, selected)] +
+                                ([(frame_i, identity.planes())] if starting is not None else []), H, W)
 
         metas = {}
         for t, plan, (flow, occl, sigma, chosen) in zip(running, plans, selected):
@@ -240,7 +251,7 @@ class MultiTemplateMFT(MFT):
             t.cleanup_memory()
             metas[t.start_frame_i] = self._meta(result)
         if starting is not None:
-            result = FlowOUTrackingResult.identity((H, W), device=self.device)
+            result = identity
             starting.memory = {frame_i: {'img': input_img, 'result': result}}
             metas[frame_i] = self._meta(result)
         self.current_frame_i = frame_i
@@ -253,6 +264,46 @@ class MultiTemplateMFT(MFT):
         self._read_out(frame_i)
         self.stats["frames"] += 1
         return metas
+
+    def _append_stores(self, frame_i, results, H, W):
+        """C.multi_template_stores: results = [(start_frame, (flow, occl, sigma))] of every template at ``frame_i``, the starting
+        one's identity included -> each template's ``DenseTrackStore`` (``track_stores[start]``, made here for the starting one)
+        gets its frame: what ``MFT`` with ``C.track_store`` keeps for that start frame alone, word for word.  With the HIP
+        backend ONE ``trackstore_append_multi`` call quantises all of them; otherwise each store appends through its own path.
+        ``C.track_store_max_bytes`` bounds the SUM over the stores: ``MemoryError`` before anything of this frame is stored."""
+        from .trackstore import DenseTrackStore
+        kw = {}
+        if self.C.track_store_frames_per_chunk:
+            kw["frames_per_chunk"] = int(self.C.track_store_frames_per_chunk)
+        stores = {s: self.track_stores[s] if s in self.track_stores else DenseTrackStore(H, W, device=self.device, **kw)
+                  for s, _ in results}
+        cap = self.C.track_store_max_bytes
+        if isinstance(cap, (int, float)) and not isinstance(cap, bool):
+            held = sum(st.nbytes for st in self.track_stores.values())
+            more = sum(st.chunk_bytes for st in stores.values() if st.next_needs_chunk)
+            if held + more > int(cap):
+                raise MemoryError(f"MultiTemplateMFT: frame {frame_i} needs {more} more bytes of track stores, which would exceed "
+                                  f"track_store_max_bytes = {int(cap)} ({held} bytes held by {len(self.track_stores)} stores)")
+        # nothing of the frame stays behind if a store cannot take it or the call fails: the reservations are given back and a
+        # store made for a template that starts here is not kept
+        done = []
+        try:
+            if self._native:
+                slots = []
+                for s, _ in results:
+                    slots.append(stores[s].reserve(frame_i))
+                    done.append(s)
+                ops.trackstore_append_multi([(planes, packed, lohi) for (_, planes), (_, packed, lohi) in zip(results, slots)])
+            else:
+                for s, planes in results:
+                    stores[s].append(planes, frame_i)
+                    done.append(s)
+        except BaseException:
+            for s in done:
+                stores[s].unreserve(frame_i)
+            raise
+        self.track_stores.update(stores)
+        self.stats["store_append_calls"] += 1 if self._native else len(results)
 
     @staticmethod
     def _meta(result):

@@ -975,6 +975,34 @@ def trackstore_append(planes, packed, lohi):
     return packed, lohi
 
 
+TRACKSTORE_APPEND_MULTI_FRAMES = 64      # frames per argument block of mftx_trackstore_append_multi (csrc/trackstore.hip: TSM_F)
+_trackstore_multi_ws = {}
+
+
+def trackstore_append_multi(frames):
+    """``trackstore_append`` for T results in one call (``mftx_trackstore_append_multi``): frames = T x (planes, packed, lohi) as
+    for ``trackstore_append``, all of one H x W and on one device.  Two launches per 64 frames; frame j's ``packed`` and ``lohi``
+    are bitwise what ``trackstore_append`` gives for it alone.  The workspace is kept per device and grows with T (it is used
+    on the current stream only, like ``trackstore_append``'s).  No host sync."""
+    lib = _lib.load()
+    frames = list(frames)
+    T = len(frames)
+    if T == 0:
+        return
+    _, H, W = frames[0][0][0].shape
+    H, W = int(H), int(W)
+    cols = [_planes(planes, H, W) for planes, _, _ in frames]
+    outs = [_trackstore_frame(packed, lohi, H, W) for _, packed, lohi in frames]
+    dev = frames[0][1].device
+    need = lib.mftx_trackstore_append_multi_workspace_bytes(T)
+    ws = _trackstore_multi_ws.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _trackstore_multi_ws[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+    arrs = [_lib.ptr_array(list(c)) for c in zip(*cols)] + [_lib.ptr_array(list(c)) for c in zip(*outs)]
+    check(lib.mftx_trackstore_append_multi(T, arrs[0][0], arrs[1][0], arrs[2][0], H, W, arrs[3][0], arrs[4][0], ws.data_ptr(),
+                                           ws.numel(), _stream()), "mftx_trackstore_append_multi")
+
+
 def trackstore_unpack(packed, lohi, out=None):
     """One stored frame -> (flow[2,H,W], occl[1,H,W], sigma[1,H,W]) on the device (``mftx_trackstore_unpack``): per channel
     bitwise ``dequantize_u16`` with the (min, max) of ``lohi``, which stay on the device.  ``out``: planes to write into."""
@@ -1116,6 +1144,93 @@ def trackstore_invert(chunks, lohi_chunks, slots, table, cell, occlusion_thresho
     check(lib.mftx_trackstore_invert(base, base + 8 * G, G, H, W, float(occlusion_threshold), keys.data_ptr(), tp, cp, _stream()),
           "mftx_trackstore_invert")
     return table, cell
+
+
+def _trackstore_frame_ptrs(frames, name):
+    """frames: J x (packed [H,W,4] uint16, lohi [4,2] float32) device views, of any stores -> (H, W, packed addresses, lohi
+    addresses) as int64 arrays."""
+    frames = list(frames)
+    if not frames:
+        raise MftxError(f"{name}: at least one stored frame")
+    H, W = int(frames[0][0].shape[0]), int(frames[0][0].shape[1])
+    ptrs = [_trackstore_frame(p, l, H, W) for p, l in frames]
+    return H, W, np.asarray([p for p, _ in ptrs], dtype=np.int64), np.asarray([l for _, l in ptrs], dtype=np.int64)
+
+
+def trackstore_locate_frames(frames, point_frame, xy, table, cell, occlusion_threshold=0.5):
+    """``trackstore_locate`` over stored frames of ANY stores, in one call (``mftx_trackstore_locate``): frames = J x (packed
+    [H,W,4], lohi [4,2]) device views; point_frame: N HOST integers, the index into ``frames`` of the frame each point is given
+    on.  xy, table, cell as for ``trackstore_locate``.  One pinned buffer, no host synchronisation.  Returns (table, cell)."""
+    lib = _lib.load()
+    H, W, pptr, lptr = _trackstore_frame_ptrs(frames, "trackstore_locate_frames")
+    if xy.dim() != 2 or int(xy.shape[1]) != 2:
+        raise MftxError("trackstore_locate_frames: xy must be [N, 2]")
+    N = int(xy.shape[0])
+    which = np.asarray(point_frame, dtype=np.int64).reshape(-1)
+    if int(which.shape[0]) != N or (N and (which.min() < 0 or which.max() >= len(pptr))):
+        raise MftxError("trackstore_locate_frames: point_frame must be N indices into frames")
+    if tuple(table.shape) != (N, 4) or tuple(cell.shape) != (N,):
+        raise MftxError("trackstore_locate_frames: the table must be [N, 4], cell [N]")
+    xp, tp, cp = _chk(xy, "xy"), _chk(table, "table"), _chk(cell, "cell", torch.int32)
+    if N == 0:
+        return table, cell
+    buf, G, off = locate_tables(which, pptr, lptr, 1, H * W * 8)         # (every frame a chunk of its own)
+    tables = torch.from_numpy(buf).pin_memory().to(xy.device, non_blocking=True)
+    keys = torch.empty(N, dtype=torch.int64, device=xy.device)
+    base = tables.data_ptr()
+    check(lib.mftx_trackstore_locate(base + off[0], base + off[1], base + off[2], G, base + off[3], base + off[4], H, W, N, xp,
+                                     float(occlusion_threshold), keys.data_ptr(), tp, cp, _stream()), "mftx_trackstore_locate")
+    return table, cell
+
+
+TRACKSTORE_ATLAS_ENTRIES = 256           # entries per plane of mftx_trackstore_invert_atlas (8 bits of its key)
+TRACKSTORE_ATLAS_CELLS = 1 << 24         # ... and cells per frame (24 bits)
+
+
+def trackstore_invert_atlas(frames, first_of, rank_of, table, cell, entry, occlusion_threshold=0.5):
+    """Stored frames of several stores inverted densely onto one plane per video frame, in one call
+    (``mftx_trackstore_invert_atlas``): frames = J x (packed [H,W,4], lohi [4,2]) device views; first_of: G + 1 HOST integers --
+    plane g is built from frames[first_of[g] : first_of[g + 1]], listed in ascending rank; rank_of: J HOST integers, what
+    ``entry`` reports for each frame.  ``table`` (float32 device [G,H,W,4]), ``cell`` and ``entry`` (int32 device [G,H,W]) receive per
+    pixel the winner's row, its template cell and its rank, -1 (and a row of NaN) where no entry finds the pixel.  H and W come
+    from ``table`` (a call may have no frames at all).  The tables go up through one pinned buffer; no host synchronisation.
+    Returns (table, cell, entry)."""
+    lib = _lib.load()
+    frames = list(frames)
+    first_of = np.asarray(first_of, dtype=np.int64).reshape(-1)
+    rank_of = np.asarray(rank_of, dtype=np.int64).reshape(-1)
+    G, J = int(first_of.shape[0]) - 1, len(frames)
+    if table.dim() != 4 or int(table.shape[3]) != 4 or int(table.shape[0]) != G or tuple(cell.shape) != tuple(table.shape[:3]) \
+            or tuple(entry.shape) != tuple(table.shape[:3]):
+        raise MftxError("trackstore_invert_atlas: the table must be [G, H, W, 4], cell and entry [G, H, W], first_of [G + 1]")
+    H, W = int(table.shape[1]), int(table.shape[2])
+    if G < 0 or int(rank_of.shape[0]) != J or first_of[0] != 0 or first_of[-1] != J or (np.diff(first_of) < 0).any():
+        raise MftxError("trackstore_invert_atlas: first_of must ascend from 0 to the number of frames, rank_of name every frame")
+    if G and np.diff(first_of).max() > TRACKSTORE_ATLAS_ENTRIES:
+        raise MftxError(f"trackstore_invert_atlas: more than {TRACKSTORE_ATLAS_ENTRIES} entries in a plane")
+    if (H - 1) * (W - 1) > TRACKSTORE_ATLAS_CELLS:
+        raise MftxError("trackstore_invert_atlas: more than 2^24 cells")
+    tp, cp, ep = _chk(table, "table"), _chk(cell, "cell", torch.int32), _chk(entry, "entry", torch.int32)
+    if J:
+        fH, fW, pptr, lptr = _trackstore_frame_ptrs(frames, "trackstore_invert_atlas")
+        if (fH, fW) != (H, W):
+            raise MftxError("trackstore_invert_atlas: the frames must be of the table's H x W")
+    else:
+        pptr = lptr = np.zeros(0, np.int64)
+    if G == 0:
+        return table, cell, entry
+    n32 = (G + 1) + J
+    buf = np.zeros(2 * J + (n32 + 1) // 2, np.int64)
+    buf[0:J], buf[J:2 * J] = pptr, lptr
+    tail = buf[2 * J:].view(np.int32)
+    tail[0:G + 1], tail[G + 1:G + 1 + J] = first_of, rank_of
+    tables = torch.from_numpy(buf).pin_memory().to(table.device, non_blocking=True)
+    keys = torch.empty(G * H * W, dtype=torch.int64, device=table.device)
+    base = tables.data_ptr()
+    check(lib.mftx_trackstore_invert_atlas(base if J else None, base + 8 * J if J else None, base + 16 * J,
+                                           base + 16 * J + 4 * (G + 1) if J else None, G, J, H, W, float(occlusion_threshold),
+                                           keys.data_ptr(), tp, cp, ep, _stream()), "mftx_trackstore_invert_atlas")
+    return table, cell, entry
 
 
 class RaftEngine:

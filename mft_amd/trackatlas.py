@@ -1,0 +1,277 @@
+"""TrackAtlas -- several ``DenseTrackStore``s of ONE video joined into one answer: every pixel of any frame followed.
+
+A ``DenseTrackStore`` answers every question about one template in one time direction, so ``locate`` / ``inverse`` return "not
+found" wherever no point of THAT template maps to -- a disoccluded region, something that entered the video after the template
+frame -- and a template in the middle of a video has its forward and backward halves in two stores.  An atlas holds one entry
+``(template_frame, store)`` per store and answers from whichever entry sees the query best::
+
+    atlas = TrackAtlas.from_passes(forward_pass, backward_pass)       # every store of MultiTemplateMFT passes (C.multi_template_stores)
+    atlas = TrackAtlas([(template_frame, store), ...])                # or any DenseTrackStores, e.g. MFT.track_store of single runs
+    table, cell, entry = atlas.locate(points, 57)                     # device [N, 4], [N], [N]; frame: one id or N ids
+    table, cell, entry = atlas.inverse(57)                            # device [H, W, 4], [H, W], [H, W]; a list of G frames: [G, ...]
+    tracks = atlas.query(template_frame, points, frames=None)         # device [N, T, 4]: points given ON that template frame
+    coords, occl, found, template = atlas.tracks_from(points, 57)     # numpy (N, T, 2), (N, T), (N,), (N,): ONE download
+
+The definition (and the ``device="cpu"`` path; there is no new arithmetic): for a query on frame ``f`` every entry whose store holds
+``f`` answers with its own ``store.locate(point, f, thr)``; among the entries that found it the smallest
+``(occlusion > thr, bits of (sigma > 0 ? sigma : +0), rank)`` wins -- ``locate``'s own key with the rank put between sigma and cell:
+visible before occluded, then lowest sigma as MFT's selection has it, then the earliest template.  ``occlusion`` and ``sigma`` are
+the row's values.  Entries are ranked by ``(template_frame, position in the argument)``.  On a template's own frame its identity
+result has sigma 0, so that template wins wherever it is visible.
+
+On the device the sparse ``locate`` is ONE ``mftx_trackstore_locate`` call (the points repeated per entry, the entries' frames as
+its groups) and a reduction by that key; the dense ``inverse`` is ONE ``mftx_trackstore_invert_atlas`` call, which scatters all
+entries of a video frame onto one key plane.  The two are different code and agree bit for bit.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+MAX_ENTRIES = 256                 # 8 bits of the dense inverse's key
+MAX_CELLS = 1 << 24               # ... and 24 for the cell: (H - 1)(W - 1)
+_NOT_FOUND = torch.iinfo(torch.int64).max
+
+
+def _same_device(a, b):
+    """'cuda' and 'cuda:0' name one card when 0 is the current device: an index that is not given is the current one."""
+    if a.type != b.type:
+        return False
+    if a.index == b.index or a.type != "cuda":
+        return a.index == b.index
+    current = torch.cuda.current_device()
+    return (current if a.index is None else a.index) == (current if b.index is None else b.index)
+
+
+class TrackAtlas:
+    def __init__(self, entries):
+        """entries: a sequence of ``(template_frame, DenseTrackStore)``, all stores of one H x W and on one device, each store's
+        first frame being its template frame (``ValueError`` otherwise, and for more than 256 entries or more than 2^24 cells)."""
+        entries = [(int(f), st) for f, st in entries]
+        if not entries:
+            raise ValueError("TrackAtlas: no entries")
+        if len(entries) > MAX_ENTRIES:
+            raise ValueError(f"TrackAtlas: {len(entries)} entries; at most {MAX_ENTRIES}")
+        first = entries[0][1]
+        self.H, self.W, self.device = first.H, first.W, first.device
+        if (self.H - 1) * (self.W - 1) > MAX_CELLS:
+            raise ValueError(f"TrackAtlas: {self.H} x {self.W} frames have more than 2^24 cells")
+        for f, st in entries:
+            if (st.H, st.W) != (self.H, self.W) or not _same_device(st.device, self.device):
+                raise ValueError(f"TrackAtlas: all stores must be {self.H} x {self.W} on {self.device}, not {st.H} x {st.W} on {st.device}")
+            if len(st) == 0 or st.frame_ids[0] != f:
+                raise ValueError(f"TrackAtlas: the first frame of template {f}'s store must be frame {f} itself "
+                                 f"(it holds {st.frame_ids[:1] or 'nothing'})")
+        order = sorted(range(len(entries)), key=lambda i: (entries[i][0], i))
+        self.entries = [entries[i] for i in order]                      # entries[rank] = (template_frame, store)
+        self.frames = sorted(set().union(*[st.frame_ids for _, st in self.entries]))
+
+    @classmethod
+    def from_passes(cls, *passes):
+        """Every store of ``MultiTemplateMFT`` passes of ONE video (``C.multi_template_stores``: ``pass.track_stores``), in the order
+        the passes are given: a template run forward and backward has its forward store at the lower rank."""
+        return cls([(s, st) for p in passes for s, st in p.track_stores.items()])
+
+    # ------------------------------------------------------------------ helpers
+    @property
+    def native(self):
+        return self.device.type != "cpu"
+
+    def _holders(self, f):
+        """The ranks of the entries whose store holds frame ``f``, ascending (``KeyError`` if none does)."""
+        ranks = [r for r, (_, st) in enumerate(self.entries) if int(f) in st._slot_of]
+        if not ranks:
+            raise KeyError(f"TrackAtlas: no entry holds frame {int(f)}")
+        return ranks
+
+    def _frame_views(self, rank, f):
+        st = self.entries[rank][1]
+        slot = st.slot_of(f)
+        return st.packed(slot), st.lohi(slot)
+
+    def _upload(self, a):
+        """A small host array -> the atlas's device, through pinned memory: no host synchronisation."""
+        t = torch.from_numpy(np.ascontiguousarray(a))
+        return t.pin_memory().to(self.device, non_blocking=True) if self.native else t
+
+    def _points(self, points, name):
+        if not isinstance(points, torch.Tensor):
+            points = torch.from_numpy(np.ascontiguousarray(np.asarray(points, dtype=np.float32)))
+        if points.dim() != 2 or int(points.shape[1]) != 2:
+            raise ValueError(f"TrackAtlas.{name}: points must be (N, 2), not {tuple(points.shape)}")
+        return points.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def _reduce(self, tq, cq, ranks, thr):
+        """tq [E, n, 4], cq [E, n]: the answers of the entries ``ranks`` (ascending) to n queries -> the winner's (table [n, 4],
+        cell [n], entry [n]) by the smallest (occlusion > thr, bits of (sigma > 0 ? sigma : +0), rank) among the entries that
+        found the query."""
+        zero = torch.zeros((), dtype=torch.float32, device=self.device)
+        s = tq[:, :, 3]
+        bits = torch.where(s > 0, s, zero).contiguous().view(torch.int32).to(torch.int64)
+        occluded = (tq[:, :, 2] > torch.tensor(thr, dtype=torch.float32)).to(torch.int64)
+        rk = self._upload(np.asarray(ranks, dtype=np.int64))
+        key = (occluded << 39) | (bits << 8) | rk[:, None]
+        key = torch.where(cq >= 0, key, torch.full((), _NOT_FOUND, dtype=torch.int64, device=self.device))
+        best, arg = key.min(dim=0)                      # (the keys of the entries that found a query differ in the rank)
+        found = best != _NOT_FOUND
+        row = tq.gather(0, arg[None, :, None].expand(1, -1, 4))[0]
+        cell = cq.gather(0, arg[None, :])[0]
+        nan = torch.full((), float("nan"), dtype=torch.float32, device=self.device)
+        minus = torch.full((), -1, dtype=torch.int32, device=self.device)
+        return (torch.where(found[:, None], row, nan), torch.where(found, cell, minus),
+                torch.where(found, (best & 0xff).to(torch.int32), minus))
+
+    # ------------------------------------------------------------------ locate
+    def locate(self, points, frame, occlusion_threshold=0.5):
+        """points (N, 2) xy given ON video frame(s) ``frame`` -- one frame id, or a host sequence of N ids -> (table [N, 4], cell [N],
+        entry [N]) on the atlas's device: the winning entry's ``store.locate`` row (ITS template's x, y, occlusion, sigma) and
+        cell, and its rank (``atlas.entries[rank]``).  Where no entry finds the query: entry = cell = -1 and a row of NaN.  A
+        frame that no entry holds is a ``KeyError``.  On the device: one kernel call and a reduction, and with ``points`` a
+        device tensor no host synchronisation."""
+        xy = self._points(points, "locate")
+        N = int(xy.shape[0])
+        ids = np.asarray(frame)
+        if ids.ndim == 0:
+            groups = [(int(ids), None)]                                         # (frame, the points given on it: all)
+        elif ids.ndim == 1 and ids.shape[0] == N:
+            groups = [(int(f), np.flatnonzero(ids == f)) for f in np.unique(ids)]
+        else:
+            raise ValueError(f"TrackAtlas.locate: frame must be one frame id or {N} of them")
+        holders = [self._holders(f) for f, _ in groups]                        # KeyError before any work
+        table = torch.empty((N, 4), dtype=torch.float32, device=self.device)
+        cell = torch.empty((N,), dtype=torch.int32, device=self.device)
+        entry = torch.empty((N,), dtype=torch.int32, device=self.device)
+        if N == 0:
+            return table, cell, entry
+        thr = float(occlusion_threshold)
+        if self.native:
+            from . import ops
+            # one call: the queries of group after group, within a group entry after entry, each entry's frame a group of the kernel's
+            views, which, index = [], [], []
+            for (f, pts), ranks in zip(groups, holders):
+                n = N if pts is None else len(pts)
+                for r in ranks:
+                    which.append(np.full(n, len(views), np.int64))
+                    views.append(self._frame_views(r, f))
+                    index.append(np.arange(N) if pts is None else pts)
+            if ids.ndim == 0:
+                xq = xy.repeat(len(views), 1)
+            else:
+                xq = xy.index_select(0, self._upload(np.concatenate(index).astype(np.int64)))
+            Q = int(xq.shape[0])
+            tq = torch.empty((Q, 4), dtype=torch.float32, device=self.device)
+            cq = torch.empty((Q,), dtype=torch.int32, device=self.device)
+            ops.trackstore_locate_frames(views, np.concatenate(which), xq, tq, cq, thr)
+        q0 = 0
+        for (f, pts), ranks in zip(groups, holders):
+            n, E = N if pts is None else len(pts), len(ranks)
+            if self.native:
+                t, c = tq[q0:q0 + E * n].view(E, n, 4), cq[q0:q0 + E * n].view(E, n)
+                q0 += E * n
+            else:
+                x = xy if pts is None else xy[torch.from_numpy(pts)]
+                answers = [self.entries[r][1].locate(x, f, thr) for r in ranks]
+                t, c = torch.stack([a[0] for a in answers]), torch.stack([a[1] for a in answers])
+            wt, wc, we = self._reduce(t, c, ranks, thr)
+            if pts is None:
+                table, cell, entry = wt, wc, we
+            else:
+                at = self._upload(pts.astype(np.int64))
+                table.index_copy_(0, at, wt)
+                cell.index_copy_(0, at, wc)
+                entry.index_copy_(0, at, we)
+        return table, cell, entry
+
+    # ------------------------------------------------------------------ the dense inverse
+    def inverse(self, frame, occlusion_threshold=0.5):
+        """Video frame ``frame`` inverted at every pixel: ``locate`` with the H * W pixel centres as its points, bit for bit ->
+        (table [H, W, 4], cell [H, W], entry [H, W]) on the atlas's device; a sequence of G frame ids gives [G, H, W, 4] and
+        [G, H, W].  On the device: ONE call whatever G and the number of entries are (``mftx_trackstore_invert_atlas``: all
+        entries of a frame scattered onto one key plane, 8 + 28 bytes per pixel and plane of workspace and results instead of that per
+        entry), and no host synchronisation."""
+        ids = np.asarray(frame)
+        if ids.ndim == 0:
+            fs, lead = [int(ids)], ()
+        elif ids.ndim == 1:
+            fs, lead = [int(f) for f in ids], (int(ids.shape[0]),)
+        else:
+            raise ValueError("TrackAtlas.inverse: frame must be one frame id or a sequence of them")
+        holders = [self._holders(f) for f in fs]                               # KeyError before any work
+        H, W, G = self.H, self.W, len(fs)
+        table = torch.empty((G, H, W, 4), dtype=torch.float32, device=self.device)
+        cell = torch.empty((G, H, W), dtype=torch.int32, device=self.device)
+        entry = torch.empty((G, H, W), dtype=torch.int32, device=self.device)
+        if G and self.native:
+            from . import ops
+            views = [self._frame_views(r, f) for f, ranks in zip(fs, holders) for r in ranks]
+            first_of = np.concatenate([[0], np.cumsum([len(ranks) for ranks in holders])])
+            ops.trackstore_invert_atlas(views, first_of, [r for ranks in holders for r in ranks], table, cell, entry,
+                                        float(occlusion_threshold))
+        elif G:
+            grid = self.entries[0][1]._pixel_grid()
+            for g, f in enumerate(fs):
+                t, c, e = self.locate(grid, f, occlusion_threshold)
+                table[g], cell[g], entry[g] = t.view(H, W, 4), c.view(H, W), e.view(H, W)
+        return table.view(lead + (H, W, 4)), cell.view(lead + (H, W)), entry.view(lead + (H, W))
+
+    # ------------------------------------------------------------------ forward read-out
+    def _columns(self, template_frame, frames):
+        """-> (frames, per column the rank of the lowest-ranked entry of that template that holds the frame, or -1)."""
+        ranks = [r for r, (f, _) in enumerate(self.entries) if f == int(template_frame)]
+        if not ranks:
+            raise KeyError(f"TrackAtlas: no entry of template frame {int(template_frame)}")
+        frames = list(self.frames) if frames is None else [int(f) for f in frames]
+        return frames, [next((r for r in ranks if f in self.entries[r][1]._slot_of), -1) for f in frames]
+
+    def query(self, template_frame, points, frames=None):
+        """points (N, 2) xy given ON template frame ``template_frame``, followed through ``frames`` (default: ``atlas.frames``) ->
+        float32 [N, T, 4] on the atlas's device: per column ``store.query`` of the lowest-ranked entry of that template that
+        holds the frame -- which joins a forward and a backward store of one template -- and a row of NaN for a frame that no
+        entry of the template holds.  ``KeyError`` for a template frame without an entry.  No host synchronisation."""
+        frames, owner = self._columns(template_frame, frames)
+        xy = self._points(points, "query")
+        N, T = int(xy.shape[0]), len(frames)
+        out = torch.full((N, T, 4), float("nan"), dtype=torch.float32, device=self.device)
+        if N == 0:
+            return out
+        for r in sorted(set(owner) - {-1}):
+            cols = [k for k, o in enumerate(owner) if o == r]
+            part = self.entries[r][1].query(xy, [frames[k] for k in cols])
+            if len(cols) == T:
+                return part
+            out.index_copy_(1, self._upload(np.asarray(cols, dtype=np.int64)), part)
+        return out
+
+    def tracks_from(self, points, frame, frames=None, occlusion_threshold=0.5):
+        """points given on video frame(s) ``frame`` (as for ``locate``), followed over ``frames`` (default: ``atlas.frames``) -> numpy
+        (coords [N, T, 2], occlusion [N, T], found [N], template [N]): ``locate``, then ``query`` of the located template points
+        on the winner's template.  Columns the winner's template does not cover and points that are not found get NaN
+        coordinates and occlusion 1; ``template`` is the winner's template frame, or -1.  ONE download; it synchronises.  To
+        keep it at one download, ALL N points are read out on every distinct template frame of the atlas and each point keeps
+        its winner's row: E_templates x N x T rows of work and E_templates temporary [N, T, 4] tables -- meant for sparse
+        points (a click, a query grid), not for every pixel of a frame."""
+        table, cell, entry = self.locate(points, frame, occlusion_threshold)
+        N = int(table.shape[0])
+        found = entry >= 0
+        zero = torch.zeros((), dtype=torch.float32, device=self.device)
+        at = torch.where(found[:, None], table[:, 0:2], zero)
+        tmpl_of = self._upload(np.asarray([f for f, _ in self.entries], dtype=np.int64))
+        minus = torch.full((), -1, dtype=torch.int64, device=self.device)
+        template = torch.where(found, tmpl_of[entry.clamp(min=0).to(torch.int64)], minus)
+        cols = list(self.frames) if frames is None else [int(f) for f in frames]
+        T = len(cols)
+        tracks = torch.full((N, T, 4), float("nan"), dtype=torch.float32, device=self.device)
+        covered = {}
+        for s in sorted({f for f, _ in self.entries}):
+            covered[s] = np.asarray(self._columns(s, cols)[1]) >= 0
+            if N and T:
+                tracks = torch.where((template == s)[:, None, None], self.query(s, at, cols), tracks)
+        both = torch.cat([tracks.reshape(N, T * 4), template.to(torch.float32)[:, None]], dim=1).cpu().numpy()
+        tracks, template = both[:, :T * 4].reshape(N, T, 4), both[:, T * 4].astype(np.int64)
+        found = template >= 0
+        coords, occl = tracks[:, :, 0:2].copy(), tracks[:, :, 2].copy()
+        lost = np.ones((N, T), bool)
+        for s, cov in covered.items():
+            lost[template == s] = ~cov
+        coords[lost], occl[lost] = np.nan, 1.0
+        return coords, occl, found, template

@@ -191,21 +191,49 @@ class DenseTrackStore:
         self._lohi.append(torch.zeros((self.frames_per_chunk, 4, 2), dtype=torch.float32, device=self.device))
 
     # ------------------------------------------------------------------ append
+    @property
+    def next_needs_chunk(self):
+        """Whether the next frame opens a new chunk (``chunk_bytes`` more of storage)."""
+        return len(self.frame_ids) == len(self._chunks) * self.frames_per_chunk
+
+    def _next_slot(self, frame_i):
+        """-> (frame id, the slot the next frame takes), its chunk allocated; nothing is registered yet."""
+        frame_i = len(self.frame_ids) if frame_i is None else int(frame_i)
+        if frame_i in self._slot_of:
+            raise ValueError(f"DenseTrackStore: frame {frame_i} is stored already (slot {self._slot_of[frame_i]})")
+        if self.next_needs_chunk:
+            self._grow()
+        return frame_i, len(self.frame_ids)
+
+    def reserve(self, frame_i=None):
+        """Take the next slot for frame ``frame_i`` whose words are written from OUTSIDE -- a multi-template pass quantises the
+        results of all its templates in one call (``ops.trackstore_append_multi``) -> (slot, packed view [H, W, 4] uint16, lohi
+        view [4, 2] float32).  The frame counts as stored from here on; the caller writes both views, on the stream the
+        store's readers use, before anything reads them.  Ids and ``max_bytes`` as for ``append``."""
+        frame_i, slot = self._next_slot(frame_i)
+        self.frame_ids.append(frame_i)
+        self._slot_of[frame_i] = slot
+        return slot, self.packed(slot), self.lohi(slot)
+
+    def unreserve(self, frame_i):
+        """Give the LAST slot back: frame ``frame_i`` was reserved and its words were never written (the call that was to write
+        them failed).  The chunk stays allocated.  ``ValueError`` unless the frame holds the last slot."""
+        frame_i = int(frame_i)
+        if not self.frame_ids or self.frame_ids[-1] != frame_i:
+            raise ValueError(f"DenseTrackStore: frame {frame_i} does not hold the last slot")
+        self.frame_ids.pop()
+        del self._slot_of[frame_i]
+
     def append(self, result_or_planes, frame_i=None):
         """Store one result -- a ``FlowOUTrackingResult`` or its (flow[2,H,W], occl[1,H,W], sigma[1,H,W]) planes -- as frame
         ``frame_i`` (default: the number of frames stored so far) and return its slot.  Frames may come in any order, each id
         once (``ValueError``).  On the device this enqueues two kernels on the current stream and never waits for the GPU."""
         planes = result_or_planes.planes() if hasattr(result_or_planes, "planes") else tuple(result_or_planes)
-        frame_i = len(self.frame_ids) if frame_i is None else int(frame_i)
-        if frame_i in self._slot_of:
-            raise ValueError(f"DenseTrackStore: frame {frame_i} is stored already (slot {self._slot_of[frame_i]})")
         flow, occl, sigma = planes
         if tuple(flow.shape) != (2, self.H, self.W) or tuple(occl.shape) != (1, self.H, self.W) or \
                 tuple(sigma.shape) != (1, self.H, self.W):
             raise ValueError(f"DenseTrackStore: planes must be [2,H,W], [1,H,W], [1,H,W] with H x W = {self.H} x {self.W}")
-        slot = len(self.frame_ids)
-        if slot == len(self._chunks) * self.frames_per_chunk:
-            self._grow()
+        frame_i, slot = self._next_slot(frame_i)
         chunk, k = slot // self.frames_per_chunk, slot % self.frames_per_chunk
         if self.native:
             from . import ops
