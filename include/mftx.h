@@ -695,6 +695,27 @@ int mftx_trackstore_invert_atlas(const uint16_t *const *frames, const float *con
                                  const int *rank_of /* [J] */, int G, int J, int H, int W, float occlusion_threshold,
                                  unsigned long long *keys /* [G*H*W] */, float *table, int *cell, int *entry, void *stream);
 
+/* The dense results FROM one video frame to T frames, across the templates of a track atlas: what mftx_trackstore_invert_atlas
+ * leaves for that frame, followed per pixel on its winner's template.  DEVICE memory throughout:
+ *   table [H][W][4] float32 (16-byte aligned) and entry [H][W] int32: one plane of mftx_trackstore_invert_atlas -- per pixel
+ *   the winner's template point (Px, Py), occlusion o_src and sigma s_src there, and the winner's rank, -1 = not found;
+ *   row_of [n_ranks] int32: rank -> row, a row being a distinct template; frames [R * T] / lohis [R * T] (pointer tables, 8-byte
+ *   aligned): row r, column t is the packed frame ([H][W][4] uint16) and its [4][2] float32 table that column t is read from
+ *   on template r, both NULL where that template does not cover the column;
+ *   flow [T][2][H][W], occl [T][H][W], sigma [T][H][W] float32 (4-byte aligned): the results.
+ * Per found pixel (x, y) and covered column the frame is sampled at (Px, Py) exactly as mftx_trackstore_query samples it -- the
+ * same set-up, taps, dequantisation and order of summation, so bit for bit its (qx, qy, o_dst, s_dst) -- and
+ *   flow = (qx - x, qy - y), occl = max(o_src, o_dst) with a NaN of either operand kept, sigma = sqrt(s_src^2 + s_dst^2):
+ * products and sum in float32, operation by operation, the root correctly rounded (taken in float64 and rounded once).  A
+ * pixel that is not found (entry outside 0 .. n_ranks - 1, or a row outside 0 .. R - 1) and a column whose pointers are NULL
+ * get flow NaN (0x7fc00000), occl 1, sigma +inf, and nothing is loaded for them.
+ * ONE launch: pixel blocks of 256 x column blocks of columns_per_block columns (0: the default, 16), a lane per pixel walking
+ * its block's columns with 4 columns' taps in flight; at most 65535 column blocks.  No allocation, no copy, no synchronisation.
+ * H * W < 2^31.  T == 0: nothing is done, 0 is returned. */
+int mftx_trackstore_flow_from(const float *table, const int *entry, const int *row_of, const uint16_t *const *frames,
+                              const float *const *lohis, int n_ranks, int R, int T, int H, int W, int columns_per_block,
+                              float *flow, float *occl, float *sigma, void *stream);
+
 /* ---- 8f-4: frame / result transport without copy queues -------------------------------------------------------------------
  * A copy KERNEL: src -> dst, n bytes, both 16-byte aligned; either may be PINNED HOST memory (hipHostMalloc / torch
  * pin_memory: mapped into the device's address space), which a kernel reads and writes over PCIe directly.  Unlike

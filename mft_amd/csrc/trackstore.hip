@@ -13,6 +13,8 @@
 //            kernel.  Bitwise the numpy float32 restatement in mft_amd/trackstore.py.
 //   invert : locate at every pixel centre of stored frames, as a scatter: each template cell writes its key onto the pixel
 //            centres its box holds; the same resolve.  Bitwise locate with the pixel grid as its queries.
+//   flow_from : a plane of the atlas's inverse followed over T columns, each pixel on its winner's template -- query's sampler and
+//            the chaining rule of DenseTrackStore.results_from in one launch, straight to planar flow, occlusion and sigma.
 //
 // Planes are read and written one float per lane (four pixels per thread in flight): their bases need 4-byte alignment only
 // (flow y of a [2][H][W] tensor and the planes of a [4][H][W] buffer sit H * W floats apart, which is no multiple of 16
@@ -580,6 +582,105 @@ __global__ __launch_bounds__(256) void ts_atlas_resolve_kernel(const uint2 *cons
     entry_out[n] = entry;
 }
 
+// ---- flow_from: the dense results FROM a video frame to T frames, across the templates of a track atlas -----------------------------
+// What invert_atlas leaves per pixel of the source frame -- the winner's template point (Px, Py), its occlusion and sigma there,
+// and the winner's rank -- followed through the columns' stored frames of THAT winner's template: ts_query_kernel's read-out of
+// (Px, Py) and the chaining rule of DenseTrackStore.results_from, straight to planar results.  A lane owns a pixel, lanes along
+// x: neighbouring pixels mostly share a winner and map to neighbouring template points, so their taps share cache lines, and
+// each of the four output planes of a column leaves as contiguous 256-byte runs per wave.  The lane reads its table row and
+// entry, looks up its row and sets the sampler up ONCE, then walks its workgroup's columns TF_FW at a time, all their taps in
+// flight.  The winner differs between lanes, so the columns' frame and lohi pointers are per-lane loads from the [R][T] tables.
+// A lane that is not found and a column its template does not cover load nothing and write the fill (NaN, NaN, 1, +inf).
+// Grid: pixel blocks x column blocks of `cols` columns -- ONE launch.
+constexpr int TF_FW = 4;            // columns whose taps a lane keeps in flight
+constexpr int TF_COLS = 16;         // columns per workgroup unless the caller says otherwise
+
+__global__ __launch_bounds__(256) void ts_flow_from_kernel(const float4 *__restrict__ table, const int *__restrict__ entry,
+                                                           const int *__restrict__ row_of, const uint2 *const *__restrict__ frames,
+                                                           const float *const *__restrict__ lohis, int n_ranks, int R, int T, int cols,
+                                                           int H, int W, float sx, float sy, float *__restrict__ flow,
+                                                           float *__restrict__ occl, float *__restrict__ sigma) {
+    const long long n = (long long)H * W;
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const long long first = (long long)blockIdx.y * cols;
+    if (first >= T) return;
+    const int t0 = (int)first, t1 = (int)(first + cols < T ? first + cols : T);
+    const int e = entry[p];
+    int row = -1;
+    if (e >= 0 && e < n_ranks) row = row_of[e];
+    const bool found = row >= 0 && row < R;             // (a table that is not what it should be reads nothing)
+    float4 src = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (found) src = table[p];
+    const float x = (float)(int)(p % W), y = (float)(int)(p / W);
+    // ts_query_kernel's sampler set-up at the template point, once per pixel
+    const float px = src.x, py = src.y;
+    const float ix = ((px * sx - 1.f) + 1.f) / 2.f * (float)(W - 1);
+    const float iy = ((py * sy - 1.f) + 1.f) / 2.f * (float)(H - 1);
+    const float flx = floorf(ix), fly = floorf(iy);
+    const float wx = ix - flx, wy = iy - fly;
+    const int x0 = (int)fminf(fmaxf(flx, -1.0e6f), 1.0e6f);
+    const int y0 = (int)fminf(fmaxf(fly, -1.0e6f), 1.0e6f);
+    const float w00 = (1.f - wx) * (1.f - wy), w01 = wx * (1.f - wy), w10 = (1.f - wx) * wy, w11 = wx * wy;
+    const bool inx0 = x0 >= 0 && x0 < W, inx1 = x0 + 1 >= 0 && x0 + 1 < W, iny0 = y0 >= 0 && y0 < H, iny1 = y0 + 1 >= 0 && y0 + 1 < H;
+    const int cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x0 + 1, 0), W - 1), cy0 = min(max(y0, 0), H - 1), cy1 = min(max(y0 + 1, 0), H - 1);
+    const long long o00 = (long long)cy0 * W + cx0, o01 = (long long)cy0 * W + cx1, o10 = (long long)cy1 * W + cx0, o11 = (long long)cy1 * W + cx1;
+    const long long tb = (long long)(found ? row : 0) * T;
+    const float nan = __uint_as_float(0x7fc00000u), inf = __uint_as_float(0x7f800000u);
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int t = t0; t < t1; t += TF_FW) {
+        const uint2 *frame[TF_FW];
+        const float *lh[TF_FW];
+        bool ok[TF_FW];
+#pragma unroll
+        for (int u = 0; u < TF_FW; ++u) {
+            frame[u] = nullptr; lh[u] = nullptr;
+            if (found && t + u < t1) { frame[u] = frames[tb + t + u]; lh[u] = lohis[tb + t + u]; }
+        }
+        uint2 q[TF_FW][4];
+        float l[TF_FW][8];
+#pragma unroll
+        for (int u = 0; u < TF_FW; ++u) {
+            ok[u] = frame[u] != nullptr && lh[u] != nullptr;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) q[u][k] = make_uint2(0u, 0u);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) l[u][k] = 0.f;
+            if (ok[u]) {
+                q[u][0] = frame[u][o00]; q[u][1] = frame[u][o01]; q[u][2] = frame[u][o10]; q[u][3] = frame[u][o11];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) l[u][k] = lh[u][k];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < TF_FW; ++u) {
+            if (t + u >= t1) continue;
+            const Dec4 dec(l[u]);
+            const float4 t00 = iny0 && inx0 ? dec(q[u][0]) : zero, t01 = iny0 && inx1 ? dec(q[u][1]) : zero;
+            const float4 t10 = iny1 && inx0 ? dec(q[u][2]) : zero, t11 = iny1 && inx1 ? dec(q[u][3]) : zero;
+            // query's row, in its order of summation ...
+            const float qx = px + (t00.x * w00 + t01.x * w01 + t10.x * w10 + t11.x * w11);
+            const float qy = py + (t00.y * w00 + t01.y * w01 + t10.y * w10 + t11.y * w11);
+            const float od = t00.z * w00 + t01.z * w01 + t10.z * w10 + t11.z * w11;
+            const float sd = t00.w * w00 + t01.w * w01 + t10.w * w10 + t11.w * w11;
+            // ... chained behind the inverse.  The maximum keeps a NaN of either operand, as torch.maximum does (fmaxf drops it).
+            // The root is taken in float64 and rounded once, as DenseTrackStore.results_from takes it: the float32 sum is exact in
+            // float64, its float64 root is correctly rounded, and because 53 >= 2 * 24 + 2 rounding that once more gives the
+            // correctly rounded float32 root -- whatever this unit's float32 sqrtf is compiled to.
+            const float ss = src.w * src.w + sd * sd;
+            float fx = qx - x, fy = qy - y;
+            float oc = src.z != src.z ? src.z : (od != od ? od : fmaxf(src.z, od));
+            float sg = (float)sqrt((double)ss);
+            if (!ok[u]) { fx = nan; fy = nan; oc = 1.f; sg = inf; }
+            const long long c = t + u;
+            flow[2 * c * n + p] = fx;
+            flow[(2 * c + 1) * n + p] = fy;
+            occl[c * n + p] = oc;
+            sigma[c * n + p] = sg;
+        }
+    }
+}
+
 static int ts_blocks(long long n) {
     const long long b = (n + (long long)TS_T * TS_PX - 1) / ((long long)TS_T * TS_PX);
     return (int)(b < 1 ? 1 : (b > TS_B_MAX ? TS_B_MAX : b));
@@ -805,4 +906,38 @@ extern "C" int mftx_trackstore_invert_atlas(const uint16_t *const *frames, const
     hipLaunchKernelGGL(ts_atlas_resolve_kernel, dim3((unsigned)(blocks * G)), dim3(256), 0, s, reinterpret_cast<const uint2 *const *>(frames),
                        lohis, first_of, rank_of, (int)blocks, H, W, keys, table, cell, entry);
     return check_launch("trackstore_invert_atlas");
+}
+
+extern "C" int mftx_trackstore_flow_from(const float *table, const int *entry, const int *row_of, const uint16_t *const *frames,
+                                         const float *const *lohis, int n_ranks, int R, int T, int H, int W, int columns_per_block,
+                                         float *flow, float *occl, float *sigma, void *stream) {
+    if (T < 0) return fail(MFTX_E_ARG, "trackstore_flow_from: need T >= 0");
+    if (H < 2 || W < 2) return fail(MFTX_E_ARG, "trackstore_flow_from: H and W must be >= 2");
+    if (columns_per_block < 0) return fail(MFTX_E_ARG, "trackstore_flow_from: columns_per_block must be >= 0 (0: the default)");
+    if (T == 0) return 0;
+    if (n_ranks < 1 || R < 1) return fail(MFTX_E_ARG, "trackstore_flow_from: need n_ranks >= 1, R >= 1");
+    const struct { const void *p; const char *name; } ptrs[] = {{table, "table"}, {entry, "entry"}, {row_of, "row_of"}, {frames, "frames"},
+                                                                {lohis, "lohis"}, {flow, "flow"}, {occl, "occl"}, {sigma, "sigma"}};
+    for (const auto &a : ptrs)
+        if (!a.p) return fail(MFTX_E_ARG, "trackstore_flow_from: null pointer: %s", a.name);
+    if ((long long)H * W > 0x7fffffffLL) return fail(MFTX_E_ARG, "trackstore_flow_from: more than 2^31 - 1 pixels");
+    const int cols = columns_per_block ? columns_per_block : TF_COLS;
+    const long long blocks = ((long long)H * W + 255) / 256, col_blocks = ((long long)T + cols - 1) / cols;
+    if (col_blocks > 65535)
+        return fail(MFTX_E_ARG, "trackstore_flow_from: T = %d in blocks of %d columns: more than 65535 column blocks", T, cols);
+    if (!aligned16(table)) return fail(MFTX_E_ALIGN, "trackstore_flow_from: table must be 16-byte aligned");
+    if (!aligned_to(frames, 8) || !aligned_to(lohis, 8))
+        return fail(MFTX_E_ALIGN, "trackstore_flow_from: the pointer tables frames and lohis must be 8-byte aligned");
+    for (const auto &a : ptrs)
+        if (!aligned_to(a.p, 4)) return fail(MFTX_E_ALIGN, "trackstore_flow_from: %s must be 4-byte aligned", a.name);
+    // np.array([2/(W-1), 2/(H-1)]).astype(np.float32), as mftx_trackstore_query has them
+    const float sx = (float)(2.0 / (double)(W - 1)), sy = (float)(2.0 / (double)(H - 1));
+    hipStream_t s = (hipStream_t)stream;
+    // per pixel and column block: a table row and an entry; per pixel and column: two pointers, a lohi table (shared between the
+    // lanes of one winner), 4 taps of 8 B, 16 B of results
+    ProfScope prof(PC_CHAIN, s, 20.0 * (double)H * W * (double)col_blocks + (32.0 + 16.0) * (double)H * W * (double)T);
+    hipLaunchKernelGGL(ts_flow_from_kernel, dim3((unsigned)blocks, (unsigned)col_blocks), dim3(256), 0, s,
+                       reinterpret_cast<const float4 *>(table), entry, row_of, reinterpret_cast<const uint2 *const *>(frames), lohis, n_ranks,
+                       R, T, cols, H, W, sx, sy, flow, occl, sigma);
+    return check_launch("trackstore_flow_from");
 }

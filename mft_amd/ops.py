@@ -1233,6 +1233,68 @@ def trackstore_invert_atlas(frames, first_of, rank_of, table, cell, entry, occlu
     return table, cell, entry
 
 
+TRACKSTORE_FLOW_COLUMNS = 16             # columns per workgroup of mftx_trackstore_flow_from unless the caller says otherwise
+
+
+def trackstore_slot_addresses(chunks, lohi_chunks, slots):
+    """The device addresses of stored frames: chunks / lohi_chunks as for ``trackstore_query``; slots: HOST integers, -1 for
+    "no frame" -> (packed addresses, lohi addresses) as int64 arrays of the slots' shape, 0 where the slot is -1."""
+    chunks, lohi_chunks = list(chunks), list(lohi_chunks)
+    if not chunks or len(chunks) != len(lohi_chunks):
+        raise MftxError("trackstore_slot_addresses: as many lohi tables as chunks, at least one")
+    fpc, H, W = (int(s) for s in chunks[0].shape[:3])
+    for c, l in zip(chunks, lohi_chunks):
+        if tuple(c.shape) != (fpc, H, W, 4) or tuple(l.shape) != (fpc, 4, 2):
+            raise MftxError("trackstore_slot_addresses: chunks must be [frames_per_chunk,H,W,4] with lohi [frames_per_chunk,4,2]")
+    slots = np.asarray(slots, dtype=np.int64)
+    if slots.size and (slots.min() < -1 or slots.max() >= fpc * len(chunks)):
+        raise MftxError("trackstore_slot_addresses: slots must be slots of the store, or -1")
+    cptr = np.asarray([_chk(c, "chunk", torch.uint16) for c in chunks], dtype=np.int64)
+    lptr = np.asarray([_chk(l, "lohi chunk") for l in lohi_chunks], dtype=np.int64)
+    held = slots >= 0
+    chunk, within = np.where(held, slots // fpc, 0), np.where(held, slots % fpc, 0)
+    return np.where(held, cptr[chunk] + within * (H * W * 8), 0), np.where(held, lptr[chunk] + within * 32, 0)
+
+
+def trackstore_flow_from(table, entry, row_of, frame_ptrs, lohi_ptrs, flow, occl, sigma, columns_per_block=0):
+    """One plane of ``trackstore_invert_atlas`` followed densely over T columns, in one call (``mftx_trackstore_flow_from``).
+    table (float32 device [H,W,4]) and entry (int32 device [H,W]): the plane; row_of: n_ranks HOST integers, rank -> row (a row
+    is a distinct template); frame_ptrs / lohi_ptrs: HOST int64 [R, T], the addresses (``trackstore_slot_addresses``) of the
+    stored H x W frame column t is read from on row r's template and of its lohi table, both 0 where that template does not
+    cover the column.  ``flow`` (float32 device [T,2,H,W]), ``occl`` and ``sigma`` ([T,1,H,W]) receive per pixel and column the
+    winner's ``trackstore_query`` of its template point chained behind the inverse (flow = q - pixel, occlusion = maximum, sigma =
+    root of the sum of squares), and NaN, 1, +inf where the pixel is not found or the column not covered.
+    ``columns_per_block``: the columns a workgroup walks (0: TRACKSTORE_FLOW_COLUMNS).  The tables go up through one pinned
+    buffer; no host synchronisation.  Returns (flow, occl, sigma)."""
+    lib = _lib.load()
+    row_of = np.asarray(row_of, dtype=np.int64).reshape(-1)
+    frame_ptrs, lohi_ptrs = np.asarray(frame_ptrs, dtype=np.int64), np.asarray(lohi_ptrs, dtype=np.int64)
+    if table.dim() != 3 or int(table.shape[2]) != 4 or tuple(entry.shape) != tuple(table.shape[:2]):
+        raise MftxError("trackstore_flow_from: the table must be [H, W, 4], entry [H, W]")
+    H, W = int(table.shape[0]), int(table.shape[1])
+    if frame_ptrs.ndim != 2 or frame_ptrs.shape != lohi_ptrs.shape or frame_ptrs.shape[0] < 1 or ((frame_ptrs == 0) != (lohi_ptrs == 0)).any():
+        raise MftxError("trackstore_flow_from: frame_ptrs and lohi_ptrs must be [R, T] with R >= 1, zero in the same places")
+    R, T = (int(s) for s in frame_ptrs.shape)
+    n_ranks = int(row_of.shape[0])
+    if n_ranks < 1 or row_of.min() < 0 or row_of.max() >= R:
+        raise MftxError("trackstore_flow_from: row_of must name a row for at least one rank")
+    if tuple(flow.shape) != (T, 2, H, W) or tuple(occl.shape) != (T, 1, H, W) or tuple(sigma.shape) != (T, 1, H, W):
+        raise MftxError("trackstore_flow_from: flow must be [T, 2, H, W], occl and sigma [T, 1, H, W]")
+    tp, ep = _chk(table, "table"), _chk(entry, "entry", torch.int32)
+    fp, op, sp = _chk(flow, "flow"), _chk(occl, "occl"), _chk(sigma, "sigma")
+    if T == 0:
+        return flow, occl, sigma
+    n = R * T
+    buf = np.zeros(2 * n + (n_ranks + 1) // 2, np.int64)
+    buf[0:n], buf[n:2 * n] = frame_ptrs.reshape(-1), lohi_ptrs.reshape(-1)
+    buf[2 * n:].view(np.int32)[0:n_ranks] = row_of
+    tables = torch.from_numpy(buf).pin_memory().to(table.device, non_blocking=True)
+    base = tables.data_ptr()
+    check(lib.mftx_trackstore_flow_from(tp, ep, base + 16 * n, base, base + 8 * n, n_ranks, R, T, H, W, int(columns_per_block),
+                                        fp, op, sp, _stream()), "mftx_trackstore_flow_from")
+    return flow, occl, sigma
+
+
 class RaftEngine:
     """Handle on the native refinement runtime (``mftx_raft_*``)."""
 

@@ -11,6 +11,9 @@ frame -- and a template in the middle of a video has its forward and backward ha
     table, cell, entry = atlas.inverse(57)                            # device [H, W, 4], [H, W], [H, W]; a list of G frames: [G, ...]
     tracks = atlas.query(template_frame, points, frames=None)         # device [N, T, 4]: points given ON that template frame
     coords, occl, found, template = atlas.tracks_from(points, 57)     # numpy (N, T, 2), (N, T), (N,), (N,): ONE download
+    flow, occl, sigma, found, template = atlas.results_from(57)       # device [T, 2, H, W], [T, 1, H, W] x 2, [H, W] x 2: EVERY pixel
+    result, found, template = atlas.result_from(57, 80)               # ... one column as a FlowOUTrackingResult
+    atlas.covered(template_frame)                                     # list of bool: the frames some entry of that template holds
 
 The definition (and the ``device="cpu"`` path; there is no new arithmetic): for a query on frame ``f`` every entry whose store holds
 ``f`` answers with its own ``store.locate(point, f, thr)``; among the entries that found it the smallest
@@ -22,6 +25,10 @@ result has sigma 0, so that template wins wherever it is visible.
 On the device the sparse ``locate`` is ONE ``mftx_trackstore_locate`` call (the points repeated per entry, the entries' frames as
 its groups) and a reduction by that key; the dense ``inverse`` is ONE ``mftx_trackstore_invert_atlas`` call, which scatters all
 entries of a video frame onto one key plane.  The two are different code and agree bit for bit.
+
+``results_from`` is the dense counterpart of ``tracks_from``: ``inverse``, then every pixel's template point followed by ``query`` on
+its own winner's template and chained behind the inverse as ``DenseTrackStore.results_from`` chains.  On the device that second
+step is ONE ``mftx_trackstore_flow_from`` call, which goes from the inverse's plane straight to planar results.
 """
 from __future__ import annotations
 
@@ -275,3 +282,108 @@ class TrackAtlas:
             lost[template == s] = ~cov
         coords[lost], occl[lost] = np.nan, 1.0
         return coords, occl, found, template
+
+    # ------------------------------------------------------------------ dense results from any frame
+    def covered(self, template_frame, frames=None):
+        """Per frame of ``frames`` (default: ``atlas.frames``) whether some entry of template ``template_frame`` holds it -- a list
+        of bool: where it is False, ``query`` / ``results_from`` have nothing to read for that template ("not covered", as
+        opposed to a point that is lost).  ``KeyError`` for a template frame without an entry."""
+        return [r >= 0 for r in self._columns(template_frame, frames)[1]]
+
+    def _templates(self):
+        """-> (the distinct template frames, ascending; per rank the index of its template among them)."""
+        templates = sorted({f for f, _ in self.entries})
+        return templates, [templates.index(f) for f, _ in self.entries]
+
+    def _flow_tables(self, cols):
+        """The host tables of ``ops.trackstore_flow_from`` for the columns ``cols`` -> (row_of [ranks], frame_ptrs [R, T], lohi_ptrs
+        [R, T]): a row per distinct template, column t holding the addresses of the stored frame ``query`` reads for that template
+        and frame -- the lowest-ranked entry's that holds it -- and 0 where no entry of the template does."""
+        from . import ops
+        templates, row_of = self._templates()
+        frame_ptrs, lohi_ptrs = np.zeros((len(templates), len(cols)), np.int64), np.zeros((len(templates), len(cols)), np.int64)
+        for k, s in enumerate(templates):
+            owner = np.asarray(self._columns(s, cols)[1], dtype=np.int64)
+            for r in np.unique(owner[owner >= 0]):
+                st = self.entries[r][1]
+                at = np.flatnonzero(owner == r)
+                frame_ptrs[k, at], lohi_ptrs[k, at] = ops.trackstore_slot_addresses(st._chunks, st._lohi, [st.slot_of(cols[c]) for c in at])
+        return row_of, frame_ptrs, lohi_ptrs
+
+    def _compose_results(self, table, entry, cols):
+        """The definition of ``results_from`` in torch, on the atlas's device: table [H, W, 4] and entry [H, W] of ``inverse``, the
+        located template points followed by ``query`` on each pixel's own template and chained behind the inverse by the rule
+        (and the code) of ``DenseTrackStore.results_from`` -> (flow [T, 2, H, W], occlusion [T, 1, H, W], sigma [T, 1, H, W]).  Every
+        pixel is read out on every distinct template and keeps its winner's row."""
+        H, W, T = self.H, self.W, len(cols)
+        N = H * W
+        templates, row_of = self._templates()
+        tb, rank = table.reshape(N, 4), entry.reshape(N)
+        found = rank >= 0
+        zero = torch.zeros((), dtype=torch.float32, device=self.device)
+        at = torch.where(found[:, None], tb[:, 0:2], zero)
+        row = self._upload(np.asarray(row_of, dtype=np.int64))[rank.clamp(min=0).to(torch.int64)]
+        q = torch.full((N, T, 4), float("nan"), dtype=torch.float32, device=self.device)
+        ok = torch.zeros((N, T), dtype=torch.bool, device=self.device)
+        for k, s in enumerate(templates):
+            mine = found & (row == k)
+            cov = np.asarray(self.covered(s, cols), dtype=bool)
+            if T and cov.any():
+                q = torch.where(mine[:, None, None], self.query(s, at, cols), q)
+                ok = torch.where(mine[:, None], self._upload(cov)[None, :], ok)
+        grid = self.entries[0][1]._pixel_grid()
+        flow = q[:, :, 0:2] - grid[:, None, :]
+        occl = torch.maximum(tb[:, None, 2], q[:, :, 2])
+        s_src, s_dst = tb[:, None, 3], q[:, :, 3]
+        # (the root taken in float64 and rounded once, as DenseTrackStore.results_from takes it)
+        sigma = torch.sqrt((s_src * s_src + s_dst * s_dst).to(torch.float64)).to(torch.float32)
+        flow = torch.where(ok[:, :, None], flow, torch.full((), float("nan"), dtype=torch.float32, device=self.device))
+        occl = torch.where(ok, occl, torch.ones((), dtype=torch.float32, device=self.device))
+        sigma = torch.where(ok, sigma, torch.full((), float("inf"), dtype=torch.float32, device=self.device))
+        return flow.permute(1, 2, 0).reshape(T, 2, H, W), occl.t().reshape(T, 1, H, W), sigma.t().reshape(T, 1, H, W)
+
+    def results_from(self, src, frames=None, occlusion_threshold=0.5, out=None):
+        """The dense results FROM video frame ``src`` to ``frames`` (default: ``atlas.frames``), every pixel followed on the template
+        that sees it best -> (flow [T, 2, H, W], occlusion [T, 1, H, W], sigma [T, 1, H, W], found [H, W] bool, template [H, W]
+        int32) on the atlas's device.  ``inverse(src)`` takes pixel (x, y) back to its winner's template point (Px, Py, o_src,
+        s_src); it is found iff an entry won it, and ``template`` is the winner's template frame (-1: not found).  That point is
+        followed by ``query`` on the winner's template -- (qx, qy, o_dst, s_dst) per column -- and chained as
+        ``DenseTrackStore.results_from`` chains: flow = (qx - x, qy - y), occlusion = max(o_src, o_dst), sigma =
+        sqrt(s_src^2 + s_dst^2).  A pixel that is not found, and a found pixel in a column that no entry of its template holds
+        (``covered``), get NaN flow, occlusion 1 and sigma +inf.  ``out``: a (flow, occlusion, sigma) triple of contiguous
+        float32 tensors of those shapes on the atlas's device to write into.  ``KeyError`` for a ``src`` that no entry holds,
+        ``ValueError`` for an ``out`` that does not fit, both before any work.  On the device: ``inverse``, one table upload
+        and ONE ``mftx_trackstore_flow_from`` call; no host synchronisation."""
+        self._holders(src)                                                      # KeyError before any work
+        cols = list(self.frames) if frames is None else [int(f) for f in frames]
+        H, W, T = self.H, self.W, len(cols)
+        shapes = ((T, 2, H, W), (T, 1, H, W), (T, 1, H, W))
+        if out is None:
+            out = tuple(torch.empty(s, dtype=torch.float32, device=self.device) for s in shapes)
+        else:
+            out = tuple(out)
+            if len(out) != 3 or any(not isinstance(o, torch.Tensor) or tuple(o.shape) != s or o.dtype != torch.float32 or
+                                    not _same_device(o.device, self.device) or not o.is_contiguous() for o, s in zip(out, shapes)):
+                raise ValueError(f"TrackAtlas.results_from: out must be contiguous float32 tensors {[list(s) for s in shapes]} on {self.device}")
+        table, _, entry = self.inverse(src, occlusion_threshold)
+        found = entry >= 0
+        tmpl_of = self._upload(np.asarray([f for f, _ in self.entries], dtype=np.int32))
+        template = torch.where(found, tmpl_of[entry.clamp(min=0).to(torch.int64)], torch.full((), -1, dtype=torch.int32, device=self.device))
+        if T and self.native:
+            from . import ops
+            ops.trackstore_flow_from(table, entry, *self._flow_tables(cols), *out)
+        elif T:
+            for o, v in zip(out, self._compose_results(table, entry, cols)):
+                o.copy_(v)
+        return out[0], out[1], out[2], found, template
+
+    def result_from(self, src, dst, occlusion_threshold=0.5):
+        """-> (``FlowOUTrackingResult`` of the flow from video frame ``src`` to video frame ``dst``, found [H, W] bool, template
+        [H, W] int32): one column of ``results_from``, ready for ``warp_forward_device`` / ``warp_backward`` (mask the pixels
+        that are not found, and those whose template does not cover ``dst``: their flow is NaN).  ``KeyError`` for a ``src`` or
+        a ``dst`` that no entry holds."""
+        from .results import FlowOUTrackingResult
+        self._holders(src)
+        self._holders(dst)
+        flow, occl, sigma, found, template = self.results_from(src, [dst], occlusion_threshold)
+        return FlowOUTrackingResult(flow[0], occl[0], sigma[0], validate=False), found, template
