@@ -13,8 +13,14 @@
 //            kernel.  Bitwise the numpy float32 restatement in mft_amd/trackstore.py.
 //   invert : locate at every pixel centre of stored frames, as a scatter: each template cell writes its key onto the pixel
 //            centres its box holds; the same resolve.  Bitwise locate with the pixel grid as its queries.
+//   invert_atlas : invert of several stored frames onto ONE key plane, the entry's index in the key between sigma and cell.  invert
+//            is these two kernels in their identity mode (one entry per plane, all 32 bits of the key's low word the cell).
 //   flow_from : a plane of the atlas's inverse followed over T columns, each pixel on its winner's template -- query's sampler and
 //            the chaining rule of DenseTrackStore.results_from in one launch, straight to planar flow, occlusion and sigma.
+//
+// Shared between them: TsSampler (query, flow_from: the bilinear sampler set up once per point, its taps' loads and their
+// weighted sum), ts_cell_tile (locate's search, the scatter: a tile's corners staged and the lane's InvCell), ts_solve_cell /
+// ts_mix / ts_locate_key (search, scatter, both resolves), and on the host ts_cell_grids / ts_launch_inverse.
 //
 // Planes are read and written one float per lane (four pixels per thread in flight): their bases need 4-byte alignment only
 // (flow y of a [2][H][W] tensor and the planes of a [4][H][W] buffer sit H * W floats apart, which is no multiple of 16
@@ -180,6 +186,39 @@ __global__ __launch_bounds__(TS_T) void ts_unpack_kernel(const uint2 *__restrict
     }
 }
 
+// chain.hip's sample_points_kernel sampler at one point (px, py) of an H x W frame, set up once and used on any number of stored
+// frames.  The four taps' addresses are clamped into the frame so that their loads are unconditional -- a caller issues the
+// loads of several frames before the first mix(), and they are all in flight together instead of one bounds-tested gather
+// after the other; a tap outside the frame counts as 0 in mix().
+struct TsSampler {
+    float w00, w01, w10, w11;
+    bool inx0, inx1, iny0, iny1;
+    long long o00, o01, o10, o11;
+    __device__ __forceinline__ TsSampler(float px, float py, float sx, float sy, int H, int W) {
+        const float ix = ((px * sx - 1.f) + 1.f) / 2.f * (float)(W - 1);
+        const float iy = ((py * sy - 1.f) + 1.f) / 2.f * (float)(H - 1);
+        const float flx = floorf(ix), fly = floorf(iy);
+        const float wx = ix - flx, wy = iy - fly;
+        const int x0 = (int)fminf(fmaxf(flx, -1.0e6f), 1.0e6f);
+        const int y0 = (int)fminf(fmaxf(fly, -1.0e6f), 1.0e6f);
+        w00 = (1.f - wx) * (1.f - wy); w01 = wx * (1.f - wy); w10 = (1.f - wx) * wy; w11 = wx * wy;
+        inx0 = x0 >= 0 && x0 < W; inx1 = x0 + 1 >= 0 && x0 + 1 < W; iny0 = y0 >= 0 && y0 < H; iny1 = y0 + 1 >= 0 && y0 + 1 < H;
+        const int cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x0 + 1, 0), W - 1), cy0 = min(max(y0, 0), H - 1), cy1 = min(max(y0 + 1, 0), H - 1);
+        o00 = (long long)cy0 * W + cx0; o01 = (long long)cy0 * W + cx1; o10 = (long long)cy1 * W + cx0; o11 = (long long)cy1 * W + cx1;
+    }
+    __device__ __forceinline__ void load(const uint2 *__restrict__ frame, uint2 (&q)[4]) const {
+        q[0] = frame[o00]; q[1] = frame[o01]; q[2] = frame[o10]; q[3] = frame[o11];
+    }
+    // (flow x, flow y, occlusion, sigma) at the point: the taps dequantised, in sample_points_kernel's order of summation
+    __device__ __forceinline__ float4 mix(const Dec4 &dec, const uint2 (&q)[4]) const {
+        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 t00 = iny0 && inx0 ? dec(q[0]) : zero, t01 = iny0 && inx1 ? dec(q[1]) : zero;
+        const float4 t10 = iny1 && inx0 ? dec(q[2]) : zero, t11 = iny1 && inx1 ? dec(q[3]) : zero;
+        return make_float4(t00.x * w00 + t01.x * w01 + t10.x * w10 + t11.x * w11, t00.y * w00 + t01.y * w01 + t10.y * w10 + t11.y * w11,
+                           t00.z * w00 + t01.z * w01 + t10.z * w10 + t11.z * w11, t00.w * w00 + t01.w * w01 + t10.w * w10 + t11.w * w11);
+    }
+};
+
 // ---- point read-out ---------------------------------------------------------------------------------------------------------
 // A workgroup owns a tile of TQ_P points x TQ_F requested frames.  Each of its four waves takes frames of the tile in turn with
 // its lanes over the POINTS: neighbouring query points share cache lines of that frame, and a grid of queries reads
@@ -201,20 +240,8 @@ __global__ __launch_bounds__(256) void ts_query_kernel(ChunkSet cs, int c0, int 
     const int i = blockIdx.x * TQ_P + lane;
     const int j0 = blockIdx.y * TQ_F;
     const bool have = i < N;
-    // sample_points_kernel's sampler set-up, once per point
     const float px = have ? xy[2 * (long long)i] : 0.f, py = have ? xy[2 * (long long)i + 1] : 0.f;
-    const float ix = ((px * sx - 1.f) + 1.f) / 2.f * (float)(W - 1);
-    const float iy = ((py * sy - 1.f) + 1.f) / 2.f * (float)(H - 1);
-    const float flx = floorf(ix), fly = floorf(iy);
-    const float wx = ix - flx, wy = iy - fly;
-    const int x0 = (int)fminf(fmaxf(flx, -1.0e6f), 1.0e6f);
-    const int y0 = (int)fminf(fmaxf(fly, -1.0e6f), 1.0e6f);
-    const float w00 = (1.f - wx) * (1.f - wy), w01 = wx * (1.f - wy), w10 = (1.f - wx) * wy, w11 = wx * wy;
-    // The four taps' addresses are clamped into the frame and the loads are unconditional; a tap outside counts as 0 below.
-    // So all TQ_FW frames' taps of this wave are in flight together instead of one bounds-tested gather after the other.
-    const bool inx0 = x0 >= 0 && x0 < W, inx1 = x0 + 1 >= 0 && x0 + 1 < W, iny0 = y0 >= 0 && y0 < H, iny1 = y0 + 1 >= 0 && y0 + 1 < H;
-    const int cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x0 + 1, 0), W - 1), cy0 = min(max(y0, 0), H - 1), cy1 = min(max(y0 + 1, 0), H - 1);
-    const long long o00 = (long long)cy0 * W + cx0, o01 = (long long)cy0 * W + cx1, o10 = (long long)cy1 * W + cx0, o11 = (long long)cy1 * W + cx1;
+    const TsSampler smp(px, py, sx, sy, H, W);          // once per point
     const long long frame_words = (long long)H * W;
     const uint2 *frame[TQ_FW];
     const float *lh[TQ_FW];
@@ -234,18 +261,11 @@ __global__ __launch_bounds__(256) void ts_query_kernel(ChunkSet cs, int c0, int 
     }
     uint2 q[TQ_FW][4];
 #pragma unroll
-    for (int u = 0; u < TQ_FW; ++u) { q[u][0] = frame[u][o00]; q[u][1] = frame[u][o01]; q[u][2] = frame[u][o10]; q[u][3] = frame[u][o11]; }
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int u = 0; u < TQ_FW; ++u) smp.load(frame[u], q[u]);       // all TQ_FW frames' taps of this wave in flight together
 #pragma unroll
     for (int u = 0; u < TQ_FW; ++u) {
-        const Dec4 dec(lh[u]);
-        const float4 t00 = iny0 && inx0 ? dec(q[u][0]) : zero, t01 = iny0 && inx1 ? dec(q[u][1]) : zero;
-        const float4 t10 = iny1 && inx0 ? dec(q[u][2]) : zero, t11 = iny1 && inx1 ? dec(q[u][3]) : zero;
-        if (ok[u] && have)
-            tile[lane][wave + 4 * u] = make_float4(px + (t00.x * w00 + t01.x * w01 + t10.x * w10 + t11.x * w11),
-                                                   py + (t00.y * w00 + t01.y * w01 + t10.y * w10 + t11.y * w11),
-                                                   t00.z * w00 + t01.z * w01 + t10.z * w10 + t11.z * w11,
-                                                   t00.w * w00 + t01.w * w01 + t10.w * w10 + t11.w * w11);
+        const float4 m = smp.mix(Dec4(lh[u]), q[u]);
+        if (ok[u] && have) tile[lane][wave + 4 * u] = make_float4(px + m.x, py + m.y, m.z, m.w);
     }
     __syncthreads();
     for (int e = threadIdx.x; e < TQ_P * TQ_F; e += 256) {
@@ -309,6 +329,38 @@ __device__ __forceinline__ unsigned long long ts_locate_key(float occl, float si
     return ((unsigned long long)(occl > thr ? 1u : 0u) << 63) | ((unsigned long long)(__float_as_uint(s) & 0x7fffffffu) << 32) | cell;
 }
 
+struct InvCell {                    // what a lane (or, read from it, a whole wave) needs of one cell
+    LocCell c;
+    float oa, ob, oc, od, sa, sb, sc, sd;      // the corners' occlusion and sigma
+    float lox, hix, loy, hiy;                  // the widened box: empty for a lane without a cell
+    unsigned cell;                             // key_hi | i * (W - 1) + j
+};
+
+// The workgroup's tile of TL_TH x TL_TW cells from (i0, j0) on: its corners (M x, M y, occlusion, sigma) staged into `corner`, and
+// the calling lane's cell built from them, lane li * TL_TW + lj owning cell (i0 + li, j0 + lj).
+__device__ __forceinline__ InvCell ts_cell_tile(const uint2 *__restrict__ frame, const float *__restrict__ lohi, int i0, int j0, int H,
+                                                int W, unsigned key_hi, float4 (*corner)[TL_TW + 1]) {
+    const Dec4 dec(lohi);
+    for (int e = threadIdx.x; e < (TL_TH + 1) * (TL_TW + 1); e += 256) {
+        const int ci = e / (TL_TW + 1), cj = e % (TL_TW + 1);
+        const int i = min(i0 + ci, H - 1), j = min(j0 + cj, W - 1);           // (a ragged tile's cells beyond the frame are never used)
+        const float4 t = dec(frame[(long long)i * W + j]);
+        corner[ci][cj] = make_float4((float)j + t.x, (float)i + t.y, t.z, t.w);
+    }
+    __syncthreads();
+    const int li = threadIdx.x / TL_TW, lj = threadIdx.x % TL_TW;
+    const float4 ta = corner[li][lj], tb = corner[li][lj + 1], tc = corner[li + 1][lj], td = corner[li + 1][lj + 1];
+    InvCell t = {{ta.x, ta.y, tb.x, tb.y, tc.x, tc.y, td.x, td.y}, ta.z, tb.z, tc.z, td.z, ta.w, tb.w, tc.w, td.w,
+                 FLT_MAX, -FLT_MAX, FLT_MAX, -FLT_MAX, key_hi | (unsigned)((i0 + li) * (W - 1) + (j0 + lj))};
+    if (i0 + li < H - 1 && j0 + lj < W - 1) {
+        t.lox = fminf(fminf(t.c.ax, t.c.bx), fminf(t.c.cx, t.c.dx)) - TL_EPS;
+        t.hix = fmaxf(fmaxf(t.c.ax, t.c.bx), fmaxf(t.c.cx, t.c.dx)) + TL_EPS;
+        t.loy = fminf(fminf(t.c.ay, t.c.by), fminf(t.c.cy, t.c.dy)) - TL_EPS;
+        t.hiy = fmaxf(fmaxf(t.c.ay, t.c.by), fmaxf(t.c.cy, t.c.dy)) + TL_EPS;
+    }
+    return t;
+}
+
 // Grid: cell tiles x frame groups (blockIdx.x = group * tiles + tile).  A group is the run order[group_start[g] ..
 // group_start[g + 1]) of queries given on one frame.  Each wave tests 64 queries at a time against the box of its 64 cells, a
 // query per lane; only the queries that pass are walked one by one, each lane with its own cell.
@@ -319,7 +371,7 @@ __global__ __launch_bounds__(256) void ts_locate_search_kernel(const uint2 *cons
     __shared__ float4 corner[TL_TH + 1][TL_TW + 1];       // (M x, M y, occlusion, sigma) of the tile's corners
     const int g = blockIdx.x / tiles, tile = blockIdx.x % tiles;
     const int i0 = (tile / tiles_x) * TL_TH, j0 = (tile % tiles_x) * TL_TW;
-    const uint2 *__restrict__ frame = frames[g];
+    const uint2 *__restrict__ frame = frames[g];          // (asked for before the queries: the tile's loads hang on it)
     const int lane = threadIdx.x & 63;
     // the wave's first 64 queries are fetched while the tile is staged (a group of few queries is one pass of the loop below)
     int k0 = group_start[g];
@@ -327,29 +379,9 @@ __global__ __launch_bounds__(256) void ts_locate_search_kernel(const uint2 *cons
     int p = k0 + lane < k_end ? order[k0 + lane] : -1;
     float px = 0.f, py = 0.f;
     if (p >= 0) { px = xy[2 * (long long)p]; py = xy[2 * (long long)p + 1]; }
-    const Dec4 dec(lohis[g]);
-    for (int e = threadIdx.x; e < (TL_TH + 1) * (TL_TW + 1); e += 256) {
-        const int ci = e / (TL_TW + 1), cj = e % (TL_TW + 1);
-        const int i = min(i0 + ci, H - 1), j = min(j0 + cj, W - 1);           // (a ragged tile's cells beyond the frame are never used)
-        const float4 t = dec(frame[(long long)i * W + j]);
-        corner[ci][cj] = make_float4((float)j + t.x, (float)i + t.y, t.z, t.w);
-    }
-    __syncthreads();
-    const int li = threadIdx.x / TL_TW, lj = threadIdx.x % TL_TW;
-    const bool active = i0 + li < H - 1 && j0 + lj < W - 1;
-    const unsigned cell = (unsigned)((i0 + li) * (W - 1) + (j0 + lj));
-    const float4 ta = corner[li][lj], tb = corner[li][lj + 1], tc = corner[li + 1][lj], td = corner[li + 1][lj + 1];
-    const LocCell c = {ta.x, ta.y, tb.x, tb.y, tc.x, tc.y, td.x, td.y};
-    // the cell's widened box: empty for a lane without a cell
-    float lox = FLT_MAX, hix = -FLT_MAX, loy = FLT_MAX, hiy = -FLT_MAX;
-    if (active) {
-        lox = fminf(fminf(c.ax, c.bx), fminf(c.cx, c.dx)) - TL_EPS;
-        hix = fmaxf(fmaxf(c.ax, c.bx), fmaxf(c.cx, c.dx)) + TL_EPS;
-        loy = fminf(fminf(c.ay, c.by), fminf(c.cy, c.dy)) - TL_EPS;
-        hiy = fmaxf(fmaxf(c.ay, c.by), fmaxf(c.cy, c.dy)) + TL_EPS;
-    }
-    // ... and the union over the wave's cells: a query outside it is in no lane's box
-    float wlox = lox, whix = hix, wloy = loy, whiy = hiy;
+    const InvCell t = ts_cell_tile(frame, lohis[g], i0, j0, H, W, 0u, corner);
+    // the union of the boxes of the wave's cells: a query outside it is in no lane's box
+    float wlox = t.lox, whix = t.hix, wloy = t.loy, whiy = t.hiy;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         wlox = fminf(wlox, __shfl_xor(wlox, off));
@@ -366,10 +398,10 @@ __global__ __launch_bounds__(256) void ts_locate_search_kernel(const uint2 *cons
             const float qy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(py), b));
             const int q = __builtin_amdgcn_readlane(p, b);
             unsigned long long key = TL_NONE;
-            if (qx >= lox && qx <= hix && qy >= loy && qy <= hiy) {
+            if (qx >= t.lox && qx <= t.hix && qy >= t.loy && qy <= t.hiy) {
                 float u, v;
-                if (ts_solve_cell(c, qx, qy, u, v))
-                    key = ts_locate_key(ts_mix(ta.z, tb.z, tc.z, td.z, u, v), ts_mix(ta.w, tb.w, tc.w, td.w, u, v), thr, cell);
+                if (ts_solve_cell(t.c, qx, qy, u, v))
+                    key = ts_locate_key(ts_mix(t.oa, t.ob, t.oc, t.od, u, v), ts_mix(t.sa, t.sb, t.sc, t.sd, u, v), thr, t.cell);
             }
             if (__any(key != TL_NONE)) {
 #pragma unroll
@@ -440,13 +472,6 @@ __device__ __forceinline__ void ts_centre_range(float lo, float hi, int n, int &
 
 __device__ __forceinline__ float ts_lane_f(float v, int b) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), b)); }
 
-struct InvCell {                    // what a lane (phase 1) or a whole wave (phase 2) needs of one cell
-    LocCell c;
-    float oa, ob, oc, od, sa, sb, sc, sd;      // the corners' occlusion and sigma
-    float lox, hix, loy, hiy;                  // the widened box
-    unsigned cell;
-};
-
 // the cell tested at pixel centre (x, y) of the frame whose keys start at `keys`: 0 <= x < W, 0 <= y < H is the caller's business
 __device__ __forceinline__ void ts_invert_try(const InvCell &t, int x, int y, int W, float thr, unsigned long long *__restrict__ keys) {
     const float qx = (float)x, qy = (float)y;
@@ -458,40 +483,43 @@ __device__ __forceinline__ void ts_invert_try(const InvCell &t, int x, int y, in
     }
 }
 
-// Grid: cell tiles x frames (blockIdx.x = g * tiles + tile), a cell per lane, the tile's corners staged as the search kernel
-// stages them.  Phase 1: a lane whose range holds at most TI_INLINE centres walks it.  Phase 2: the wave takes the larger cells
-// one at a time, its 64 lanes striding over the range, so that a torn cell's frame-sized box costs area / 64 solves per lane.
-// `keys` is the key plane of the frame; `key_hi` is OR-ed onto the cell in the key's low word (the atlas puts an entry's index there).
-__device__ __forceinline__ void ts_invert_scatter_body(const uint2 *__restrict__ frame, const float *__restrict__ lohi, int tile,
-                                                       int tiles_x, int H, int W, float thr, unsigned long long *__restrict__ keys,
-                                                       unsigned key_hi, float4 (*corner)[TL_TW + 1]) {
-    const int i0 = (tile / tiles_x) * TL_TH, j0 = (tile % tiles_x) * TL_TW;
+// ---- invert_atlas: several stored frames (the entries of a track atlas that hold one video frame) scattered onto ONE key plane ------
+// Plane g is built from the stored frames j = first_of[g] .. first_of[g + 1] - 1, listed in ascending rank.  Entry k = j - first_of[g]
+// goes into bits 31..24 of the key's low word, above the 24 bits of the cell: the minimum is locate's (occluded, sigma, cell) with
+// the rank put between sigma and cell, i.e. per-entry invert followed by the minimum of (occluded, sigma, rank) over the entries.
+// invert is the same two kernels in their identity mode, first_of == nullptr (uniform per launch): plane g is stored frame g
+// alone, and the key's low word is locate's -- the cell in all 32 bits, so neither limit below binds it.
+constexpr int TA_ENTRIES = 256;                 // entries per plane (8 bits of the key)
+constexpr long long TA_CELLS = 1ll << 24;       // cells per frame (24 bits of the key)
+
+// Grid: cell tiles x stored frames (blockIdx.x = j * tiles + tile), a cell per lane, the tile staged as the search kernel stages
+// it.  The plane of frame j is the last g with first_of[g] <= j.  Phase 1: a lane whose range holds at most TI_INLINE centres
+// walks it.  Phase 2: the wave takes the larger cells one at a time, its 64 lanes striding over the range, so that a torn cell's
+// frame-sized box costs area / 64 solves per lane.
+__global__ __launch_bounds__(256) void ts_atlas_scatter_kernel(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
+                                                               const int *__restrict__ first_of, int G, int tiles_x, int tiles, int H, int W,
+                                                               float thr, unsigned long long *__restrict__ keys) {
+    __shared__ float4 corner[TL_TH + 1][TL_TW + 1];
+    const int j = blockIdx.x / tiles, tile = blockIdx.x % tiles;
+    int g = j, e = 0;
+    if (first_of) {
+        int hi = G - 1;
+        g = 0;
+        while (g < hi) {
+            const int mid = (g + hi + 1) >> 1;
+            if (first_of[mid] <= j) g = mid; else hi = mid - 1;
+        }
+        e = j - first_of[g];
+        if (e < 0 || e >= TA_ENTRIES || j >= first_of[g + 1]) return;    // (block-uniform: a table that is not what it should be writes nothing)
+    }
+    keys += (long long)g * H * W;
     const int lane = threadIdx.x & 63;
-    const Dec4 dec(lohi);
-    for (int e = threadIdx.x; e < (TL_TH + 1) * (TL_TW + 1); e += 256) {
-        const int ci = e / (TL_TW + 1), cj = e % (TL_TW + 1);
-        const int i = min(i0 + ci, H - 1), j = min(j0 + cj, W - 1);           // (a ragged tile's cells beyond the frame are never used)
-        const float4 t = dec(frame[(long long)i * W + j]);
-        corner[ci][cj] = make_float4((float)j + t.x, (float)i + t.y, t.z, t.w);
-    }
-    __syncthreads();
-    const int li = threadIdx.x / TL_TW, lj = threadIdx.x % TL_TW;
-    const bool active = i0 + li < H - 1 && j0 + lj < W - 1;
-    const float4 ta = corner[li][lj], tb = corner[li][lj + 1], tc = corner[li + 1][lj], td = corner[li + 1][lj + 1];
-    InvCell t = {{ta.x, ta.y, tb.x, tb.y, tc.x, tc.y, td.x, td.y}, ta.z, tb.z, tc.z, td.z, ta.w, tb.w, tc.w, td.w,
-                 FLT_MAX, -FLT_MAX, FLT_MAX, -FLT_MAX, key_hi | (unsigned)((i0 + li) * (W - 1) + (j0 + lj))};
-    // the cell's widened box: empty for a lane without a cell
-    if (active) {
-        t.lox = fminf(fminf(t.c.ax, t.c.bx), fminf(t.c.cx, t.c.dx)) - TL_EPS;
-        t.hix = fmaxf(fmaxf(t.c.ax, t.c.bx), fmaxf(t.c.cx, t.c.dx)) + TL_EPS;
-        t.loy = fminf(fminf(t.c.ay, t.c.by), fminf(t.c.cy, t.c.dy)) - TL_EPS;
-        t.hiy = fmaxf(fmaxf(t.c.ay, t.c.by), fmaxf(t.c.cy, t.c.dy)) + TL_EPS;
-    }
+    const InvCell t = ts_cell_tile(frames[j], lohis[j], (tile / tiles_x) * TL_TH, (tile % tiles_x) * TL_TW, H, W, (unsigned)e << 24, corner);
     int x0, x1, y0, y1;
     ts_centre_range(t.lox, t.hix, W, x0, x1);
     ts_centre_range(t.loy, t.hiy, H, y0, y1);
     const int bw = max(x1 - x0 + 1, 0), bh = max(y1 - y0 + 1, 0);          // bw <= W, bh <= H: the product is at most H * W < 2^31
-    const int count = active ? bw * bh : 0;
+    const int count = bw * bh;                                             // (0 for a lane without a cell: its box is empty)
     // phase 1
     const int n1 = count <= TI_INLINE ? count : 0;
     for (int k = 0; k < n1; ++k) ts_invert_try(t, x0 + k % bw, y0 + k / bw, W, thr, keys);
@@ -512,52 +540,8 @@ __device__ __forceinline__ void ts_invert_scatter_body(const uint2 *__restrict__
     }
 }
 
-__global__ __launch_bounds__(256) void ts_invert_scatter_kernel(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
-                                                                int tiles_x, int tiles, int H, int W, float thr,
-                                                                unsigned long long *__restrict__ keys) {
-    __shared__ float4 corner[TL_TH + 1][TL_TW + 1];       // (M x, M y, occlusion, sigma) of the tile's corners
-    const int g = blockIdx.x / tiles, tile = blockIdx.x % tiles;
-    ts_invert_scatter_body(frames[g], lohis[g], tile, tiles_x, H, W, thr, keys + (long long)g * H * W, 0u, corner);
-}
-
-// One lane per pixel of frame g (blockIdx.x = g * blocks + block): the query is the pixel's centre.
-__global__ __launch_bounds__(256) void ts_invert_resolve_kernel(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
-                                                                int blocks, int H, int W, const unsigned long long *__restrict__ keys,
-                                                                float *__restrict__ table, int *__restrict__ cell_out) {
-    const int g = blockIdx.x / blocks;
-    const int p = (blockIdx.x % blocks) * 256 + threadIdx.x;
-    if (p >= H * W) return;
-    const long long n = (long long)g * H * W + p;
-    float4 row;
-    const int cell = ts_resolve(frames, lohis, g, H, W, keys[n], (float)(p % W), (float)(p / W), row);
-    *reinterpret_cast<float4 *>(table + 4 * n) = row;
-    cell_out[n] = cell;
-}
-
-// ---- invert_atlas: several stored frames (the entries of a track atlas that hold one video frame) scattered onto ONE key plane ------
-// Plane g is built from the stored frames j = first_of[g] .. first_of[g + 1] - 1, listed in ascending rank.  Entry k = j - first_of[g]
-// goes into bits 31..24 of the key's low word, above the 24 bits of the cell: the minimum is locate's (occluded, sigma, cell) with
-// the rank put between sigma and cell, i.e. per-entry invert followed by the minimum of (occluded, sigma, rank) over the entries.
-constexpr int TA_ENTRIES = 256;                 // entries per plane (8 bits of the key)
-constexpr long long TA_CELLS = 1ll << 24;       // cells per frame (24 bits of the key)
-
-// Grid: cell tiles x stored frames (blockIdx.x = j * tiles + tile).  The plane of frame j is the last g with first_of[g] <= j.
-__global__ __launch_bounds__(256) void ts_atlas_scatter_kernel(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
-                                                               const int *__restrict__ first_of, int G, int tiles_x, int tiles, int H, int W,
-                                                               float thr, unsigned long long *__restrict__ keys) {
-    __shared__ float4 corner[TL_TH + 1][TL_TW + 1];
-    const int j = blockIdx.x / tiles, tile = blockIdx.x % tiles;
-    int g = 0, hi = G - 1;
-    while (g < hi) {
-        const int mid = (g + hi + 1) >> 1;
-        if (first_of[mid] <= j) g = mid; else hi = mid - 1;
-    }
-    const int k = j - first_of[g];
-    if (k < 0 || k >= TA_ENTRIES || j >= first_of[g + 1]) return;        // (block-uniform: a table that is not what it should be writes nothing)
-    ts_invert_scatter_body(frames[j], lohis[j], tile, tiles_x, H, W, thr, keys + (long long)g * H * W, (unsigned)k << 24, corner);
-}
-
-// One lane per pixel of plane g (blockIdx.x = g * blocks + block): the winning entry's cell solved again, as ts_invert_resolve_kernel does.
+// One lane per pixel of plane g (blockIdx.x = g * blocks + block): the query is the pixel's centre, and the winning entry's cell is
+// solved again.  Identity mode has no entries: rank_of is not read, and entry_out may be null.
 __global__ __launch_bounds__(256) void ts_atlas_resolve_kernel(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
                                                                const int *__restrict__ first_of, const int *__restrict__ rank_of, int blocks,
                                                                int H, int W, const unsigned long long *__restrict__ keys,
@@ -566,20 +550,25 @@ __global__ __launch_bounds__(256) void ts_atlas_resolve_kernel(const uint2 *cons
     const int p = (blockIdx.x % blocks) * 256 + threadIdx.x;
     if (p >= H * W) return;
     const long long n = (long long)g * H * W + p;
-    const unsigned long long key = keys[n];
+    unsigned long long key = keys[n];
     const float nan = __uint_as_float(0x7fc00000u);
     float4 row = make_float4(nan, nan, nan, nan);
     int cell = -1, entry = -1;
     if (key != TL_NONE) {
-        const int j = first_of[g] + (int)((key >> 24) & 0xffu);
-        if (j < first_of[g + 1]) {
-            cell = ts_resolve(frames, lohis, j, H, W, (key & ~0xffffffffull) | (key & 0xffffffull), (float)(p % W), (float)(p / W), row);
-            if (cell >= 0) entry = rank_of[j];
+        int j = g;
+        if (first_of) {
+            j = first_of[g] + (int)((key >> 24) & 0xffu);
+            if (j >= first_of[g + 1]) j = -1;
+            key = (key & ~0xffffffffull) | (key & 0xffffffull);
+        }
+        if (j >= 0) {
+            cell = ts_resolve(frames, lohis, j, H, W, key, (float)(p % W), (float)(p / W), row);
+            if (cell >= 0) entry = first_of ? rank_of[j] : 0;
         }
     }
     *reinterpret_cast<float4 *>(table + 4 * n) = row;
     cell_out[n] = cell;
-    entry_out[n] = entry;
+    if (entry_out) entry_out[n] = entry;
 }
 
 // ---- flow_from: the dense results FROM a video frame to T frames, across the templates of a track atlas -----------------------------
@@ -613,21 +602,9 @@ __global__ __launch_bounds__(256) void ts_flow_from_kernel(const float4 *__restr
     float4 src = make_float4(0.f, 0.f, 0.f, 0.f);
     if (found) src = table[p];
     const float x = (float)(int)(p % W), y = (float)(int)(p / W);
-    // ts_query_kernel's sampler set-up at the template point, once per pixel
-    const float px = src.x, py = src.y;
-    const float ix = ((px * sx - 1.f) + 1.f) / 2.f * (float)(W - 1);
-    const float iy = ((py * sy - 1.f) + 1.f) / 2.f * (float)(H - 1);
-    const float flx = floorf(ix), fly = floorf(iy);
-    const float wx = ix - flx, wy = iy - fly;
-    const int x0 = (int)fminf(fmaxf(flx, -1.0e6f), 1.0e6f);
-    const int y0 = (int)fminf(fmaxf(fly, -1.0e6f), 1.0e6f);
-    const float w00 = (1.f - wx) * (1.f - wy), w01 = wx * (1.f - wy), w10 = (1.f - wx) * wy, w11 = wx * wy;
-    const bool inx0 = x0 >= 0 && x0 < W, inx1 = x0 + 1 >= 0 && x0 + 1 < W, iny0 = y0 >= 0 && y0 < H, iny1 = y0 + 1 >= 0 && y0 + 1 < H;
-    const int cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x0 + 1, 0), W - 1), cy0 = min(max(y0, 0), H - 1), cy1 = min(max(y0 + 1, 0), H - 1);
-    const long long o00 = (long long)cy0 * W + cx0, o01 = (long long)cy0 * W + cx1, o10 = (long long)cy1 * W + cx0, o11 = (long long)cy1 * W + cx1;
+    const TsSampler smp(src.x, src.y, sx, sy, H, W);     // ts_query_kernel's sampler at the template point, once per pixel
     const long long tb = (long long)(found ? row : 0) * T;
     const float nan = __uint_as_float(0x7fc00000u), inf = __uint_as_float(0x7f800000u);
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int t = t0; t < t1; t += TF_FW) {
         const uint2 *frame[TF_FW];
         const float *lh[TF_FW];
@@ -647,7 +624,7 @@ __global__ __launch_bounds__(256) void ts_flow_from_kernel(const float4 *__restr
 #pragma unroll
             for (int k = 0; k < 8; ++k) l[u][k] = 0.f;
             if (ok[u]) {
-                q[u][0] = frame[u][o00]; q[u][1] = frame[u][o01]; q[u][2] = frame[u][o10]; q[u][3] = frame[u][o11];
+                smp.load(frame[u], q[u]);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) l[u][k] = lh[u][k];
             }
@@ -655,14 +632,9 @@ __global__ __launch_bounds__(256) void ts_flow_from_kernel(const float4 *__restr
 #pragma unroll
         for (int u = 0; u < TF_FW; ++u) {
             if (t + u >= t1) continue;
-            const Dec4 dec(l[u]);
-            const float4 t00 = iny0 && inx0 ? dec(q[u][0]) : zero, t01 = iny0 && inx1 ? dec(q[u][1]) : zero;
-            const float4 t10 = iny1 && inx0 ? dec(q[u][2]) : zero, t11 = iny1 && inx1 ? dec(q[u][3]) : zero;
-            // query's row, in its order of summation ...
-            const float qx = px + (t00.x * w00 + t01.x * w01 + t10.x * w10 + t11.x * w11);
-            const float qy = py + (t00.y * w00 + t01.y * w01 + t10.y * w10 + t11.y * w11);
-            const float od = t00.z * w00 + t01.z * w01 + t10.z * w10 + t11.z * w11;
-            const float sd = t00.w * w00 + t01.w * w01 + t10.w * w10 + t11.w * w11;
+            const float4 m = smp.mix(Dec4(l[u]), q[u]);
+            // query's row ...
+            const float qx = src.x + m.x, qy = src.y + m.y, od = m.z, sd = m.w;
             // ... chained behind the inverse.  The maximum keeps a NaN of either operand, as torch.maximum does (fmaxf drops it).
             // The root is taken in float64 and rounded once, as DenseTrackStore.results_from takes it: the float32 sum is exact in
             // float64, its float64 root is correctly rounded, and because 53 >= 2 * 24 + 2 rounding that once more gives the
@@ -687,6 +659,37 @@ static int ts_blocks(long long n) {
 }
 
 static bool aligned_to(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
+
+// The grids of locate, invert and invert_atlas over an H x W frame: its cell tiles, one workgroup each per tile frame, and its
+// blocks of 256 pixels, one workgroup each per block plane.  `fits`: both products are grids of one launch.
+struct CellGrids { int tiles_x; long long tiles, blocks; bool fits; };
+static CellGrids ts_cell_grids(int H, int W, long long tile_frames, long long block_planes) {
+    CellGrids g;
+    g.tiles_x = cdiv(W - 1, TL_TW);
+    g.tiles = (long long)g.tiles_x * cdiv(H - 1, TL_TH);
+    g.blocks = ((long long)H * W + 255) / 256;
+    g.fits = g.tiles * tile_frames <= 0x7fffffffLL && g.blocks * block_planes <= 0x7fffffffLL;
+    return g;
+}
+
+// The launches of invert_atlas, and of invert as its identity mode (first_of and rank_of null, J == G, entry null or not): the G
+// key planes reset, the J stored frames scattered onto them, every pixel of every plane resolved.
+static int ts_launch_inverse(const char *who, const uint16_t *const *frames, const float *const *lohis, const int *first_of,
+                             const int *rank_of, int G, int J, const CellGrids &cg, int H, int W, float thr, unsigned long long *keys,
+                             float *table, int *cell, int *entry, hipStream_t s) {
+    const uint2 *const *words = reinterpret_cast<const uint2 *const *>(frames);
+    hipError_t e = hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * (size_t)G * H * W, s);
+    if (e != hipSuccess) return fail((int)e, "%s: %s", who, hipGetErrorString(e));
+    if (J > 0) {
+        hipLaunchKernelGGL(ts_atlas_scatter_kernel, dim3((unsigned)(cg.tiles * J)), dim3(256), 0, s, words, lohis, first_of, G, cg.tiles_x,
+                           (int)cg.tiles, H, W, thr, keys);
+        const int rc = check_launch(who);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(ts_atlas_resolve_kernel, dim3((unsigned)(cg.blocks * G)), dim3(256), 0, s, words, lohis, first_of, rank_of,
+                       (int)cg.blocks, H, W, keys, table, cell, entry);
+    return check_launch(who);
+}
 
 }  // namespace mftx
 
@@ -815,9 +818,8 @@ extern "C" int mftx_trackstore_locate(const uint16_t *const *frames, const float
         return fail(MFTX_E_ARG, "trackstore_locate: null pointer");
     if (G < 1 || G > N) return fail(MFTX_E_ARG, "trackstore_locate: need 1 <= G <= N frame groups");
     if ((long long)(H - 1) * (W - 1) > 0x7fffffffLL) return fail(MFTX_E_ARG, "trackstore_locate: more than 2^31 - 1 cells");
-    const int tiles_x = cdiv(W - 1, TL_TW), tiles_y = cdiv(H - 1, TL_TH);
-    const long long tiles = (long long)tiles_x * tiles_y;
-    if (tiles * G > 0x7fffffffLL) return fail(MFTX_E_ARG, "trackstore_locate: %lld cell tiles x %d frame groups exceed one grid", tiles, G);
+    const CellGrids cg = ts_cell_grids(H, W, G, 0);
+    if (!cg.fits) return fail(MFTX_E_ARG, "trackstore_locate: %lld cell tiles x %d frame groups exceed one grid", cg.tiles, G);
     if (!aligned_to(frames, 8) || !aligned_to(lohis, 8) || !aligned_to(keys, 8))
         return fail(MFTX_E_ALIGN, "trackstore_locate: the pointer tables and the keys must be 8-byte aligned");
     if (!aligned_to(group_start, 4) || !aligned_to(order, 4) || !aligned_to(group_of, 4) || !aligned_to(xy, 4) || !aligned_to(cell, 4))
@@ -825,11 +827,11 @@ extern "C" int mftx_trackstore_locate(const uint16_t *const *frames, const float
     if (!aligned16(table)) return fail(MFTX_E_ALIGN, "trackstore_locate: the table must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     // per tile and group: 33 x 9 packed corners; per query: its coordinates in every wave, a key, a row, a cell index
-    ProfScope prof(PC_CHAIN, s, 8.0 * (TL_TW + 1) * (TL_TH + 1) * (double)tiles * G + (8.0 + 8.0 + 16.0 + 4.0) * (double)N);
+    ProfScope prof(PC_CHAIN, s, 8.0 * (TL_TW + 1) * (TL_TH + 1) * (double)cg.tiles * G + (8.0 + 8.0 + 16.0 + 4.0) * (double)N);
     hipError_t e = hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * (size_t)N, s);
     if (e != hipSuccess) return fail((int)e, "trackstore_locate: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(ts_locate_search_kernel, dim3((unsigned)(tiles * G)), dim3(256), 0, s, reinterpret_cast<const uint2 *const *>(frames),
-                       lohis, group_start, order, tiles_x, (int)tiles, H, W, xy, occlusion_threshold, keys);
+    hipLaunchKernelGGL(ts_locate_search_kernel, dim3((unsigned)(cg.tiles * G)), dim3(256), 0, s, reinterpret_cast<const uint2 *const *>(frames),
+                       lohis, group_start, order, cg.tiles_x, (int)cg.tiles, H, W, xy, occlusion_threshold, keys);
     int rc = check_launch("trackstore_locate");
     if (rc) return rc;
     hipLaunchKernelGGL(ts_locate_resolve_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, reinterpret_cast<const uint2 *const *>(frames), lohis,
@@ -844,28 +846,20 @@ extern "C" int mftx_trackstore_invert(const uint16_t *const *frames, const float
     if (G == 0) return 0;
     if (!frames || !lohis || !keys || !table || !cell) return fail(MFTX_E_ARG, "trackstore_invert: null pointer");
     if ((long long)H * W > 0x7fffffffLL) return fail(MFTX_E_ARG, "trackstore_invert: more than 2^31 - 1 pixels (and cells)");
-    const int tiles_x = cdiv(W - 1, TL_TW), tiles_y = cdiv(H - 1, TL_TH);
-    const long long tiles = (long long)tiles_x * tiles_y, blocks = ((long long)H * W + 255) / 256;
-    if (tiles * G > 0x7fffffffLL || blocks * G > 0x7fffffffLL)
-        return fail(MFTX_E_ARG, "trackstore_invert: %lld cell tiles (%lld pixel blocks) x %d frames exceed one grid", tiles, blocks, G);
+    const CellGrids cg = ts_cell_grids(H, W, G, G);
+    if (!cg.fits)
+        return fail(MFTX_E_ARG, "trackstore_invert: %lld cell tiles (%lld pixel blocks) x %d frames exceed one grid", cg.tiles, cg.blocks, G);
     if (!aligned_to(frames, 8) || !aligned_to(lohis, 8) || !aligned_to(keys, 8))
         return fail(MFTX_E_ALIGN, "trackstore_invert: the pointer tables and the keys must be 8-byte aligned");
     if (!aligned_to(cell, 4)) return fail(MFTX_E_ALIGN, "trackstore_invert: cell must be 4-byte aligned");
     if (!aligned16(table)) return fail(MFTX_E_ALIGN, "trackstore_invert: the table must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    const long long n = (long long)G * H * W;
     // per tile and frame: 33 x 9 packed corners; per pixel: its key set, (at least once) lowered and read, a row, a cell index, and
     // the winning cell's four corners once more
-    ProfScope prof(PC_CHAIN, s, 8.0 * (TL_TW + 1) * (TL_TH + 1) * (double)tiles * G + (8.0 + 8.0 + 8.0 + 16.0 + 4.0 + 32.0) * (double)n);
-    hipError_t e = hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * (size_t)n, s);
-    if (e != hipSuccess) return fail((int)e, "trackstore_invert: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(ts_invert_scatter_kernel, dim3((unsigned)(tiles * G)), dim3(256), 0, s, reinterpret_cast<const uint2 *const *>(frames),
-                       lohis, tiles_x, (int)tiles, H, W, occlusion_threshold, keys);
-    int rc = check_launch("trackstore_invert");
-    if (rc) return rc;
-    hipLaunchKernelGGL(ts_invert_resolve_kernel, dim3((unsigned)(blocks * G)), dim3(256), 0, s, reinterpret_cast<const uint2 *const *>(frames),
-                       lohis, (int)blocks, H, W, keys, table, cell);
-    return check_launch("trackstore_invert");
+    ProfScope prof(PC_CHAIN, s, 8.0 * (TL_TW + 1) * (TL_TH + 1) * (double)cg.tiles * G +
+                                    (8.0 + 8.0 + 8.0 + 16.0 + 4.0 + 32.0) * (double)G * H * W);
+    return ts_launch_inverse("trackstore_invert", frames, lohis, nullptr, nullptr, G, G, cg, H, W, occlusion_threshold, keys, table, cell,
+                             nullptr, s);
 }
 
 extern "C" int mftx_trackstore_invert_atlas(const uint16_t *const *frames, const float *const *lohis, const int *first_of,
@@ -879,33 +873,22 @@ extern "C" int mftx_trackstore_invert_atlas(const uint16_t *const *frames, const
     if (G == 0) return 0;
     if (!first_of || !keys || !table || !cell || !entry || (J > 0 && (!frames || !lohis || !rank_of)))
         return fail(MFTX_E_ARG, "trackstore_invert_atlas: null pointer");
-    const int tiles_x = cdiv(W - 1, TL_TW), tiles_y = cdiv(H - 1, TL_TH);
-    const long long tiles = (long long)tiles_x * tiles_y, blocks = ((long long)H * W + 255) / 256;
-    if (tiles * J > 0x7fffffffLL || blocks * G > 0x7fffffffLL)
-        return fail(MFTX_E_ARG, "trackstore_invert_atlas: %lld cell tiles x %d frames (%lld pixel blocks x %d planes) exceed one grid", tiles, J,
-                    blocks, G);
+    const CellGrids cg = ts_cell_grids(H, W, J, G);
+    if (!cg.fits)
+        return fail(MFTX_E_ARG, "trackstore_invert_atlas: %lld cell tiles x %d frames (%lld pixel blocks x %d planes) exceed one grid", cg.tiles,
+                    J, cg.blocks, G);
     if (!aligned_to(frames, 8) || !aligned_to(lohis, 8) || !aligned_to(keys, 8))
         return fail(MFTX_E_ALIGN, "trackstore_invert_atlas: the pointer tables and the keys must be 8-byte aligned");
     if (!aligned_to(first_of, 4) || !aligned_to(rank_of, 4) || !aligned_to(cell, 4) || !aligned_to(entry, 4))
         return fail(MFTX_E_ALIGN, "trackstore_invert_atlas: first_of, rank_of, cell and entry must be 4-byte aligned");
     if (!aligned16(table)) return fail(MFTX_E_ALIGN, "trackstore_invert_atlas: the table must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    const long long n = (long long)G * H * W;
     // per tile and stored frame: 33 x 9 packed corners; per pixel of a plane: its key set and read, a row, a cell, an entry, the
     // winning cell's four corners once more; per pixel of a stored frame: (at least) one key lowered
-    ProfScope prof(PC_CHAIN, s, 8.0 * (TL_TW + 1) * (TL_TH + 1) * (double)tiles * J + (8.0 + 8.0 + 16.0 + 4.0 + 4.0 + 32.0) * (double)n +
-                                    8.0 * (double)J * H * W);
-    hipError_t e = hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * (size_t)n, s);
-    if (e != hipSuccess) return fail((int)e, "trackstore_invert_atlas: %s", hipGetErrorString(e));
-    if (J > 0) {
-        hipLaunchKernelGGL(ts_atlas_scatter_kernel, dim3((unsigned)(tiles * J)), dim3(256), 0, s, reinterpret_cast<const uint2 *const *>(frames),
-                           lohis, first_of, G, tiles_x, (int)tiles, H, W, occlusion_threshold, keys);
-        const int rc = check_launch("trackstore_invert_atlas");
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(ts_atlas_resolve_kernel, dim3((unsigned)(blocks * G)), dim3(256), 0, s, reinterpret_cast<const uint2 *const *>(frames),
-                       lohis, first_of, rank_of, (int)blocks, H, W, keys, table, cell, entry);
-    return check_launch("trackstore_invert_atlas");
+    ProfScope prof(PC_CHAIN, s, 8.0 * (TL_TW + 1) * (TL_TH + 1) * (double)cg.tiles * J +
+                                    (8.0 + 8.0 + 16.0 + 4.0 + 4.0 + 32.0) * (double)G * H * W + 8.0 * (double)J * H * W);
+    return ts_launch_inverse("trackstore_invert_atlas", frames, lohis, first_of, rank_of, G, J, cg, H, W, occlusion_threshold, keys, table,
+                             cell, entry, s);
 }
 
 extern "C" int mftx_trackstore_flow_from(const float *table, const int *entry, const int *row_of, const uint16_t *const *frames,

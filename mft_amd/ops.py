@@ -1016,6 +1016,66 @@ def trackstore_unpack(packed, lohi, out=None):
     return out
 
 
+def _trackstore_chunks(chunks, lohi_chunks, name):
+    """The chunk list every read-out takes -- uint16 device tensors [frames_per_chunk, H, W, 4] with float32 [frames_per_chunk, 4, 2]
+    beside them -- validated -> (frames_per_chunk, H, W, chunk addresses, lohi addresses)."""
+    chunks, lohi_chunks = list(chunks), list(lohi_chunks)
+    if not chunks or len(chunks) != len(lohi_chunks):
+        raise MftxError(f"{name}: as many lohi tables as chunks, at least one")
+    fpc, H, W = (int(s) for s in chunks[0].shape[:3])
+    for c, l in zip(chunks, lohi_chunks):
+        if tuple(c.shape) != (fpc, H, W, 4) or tuple(l.shape) != (fpc, 4, 2):
+            raise MftxError(f"{name}: chunks must be [frames_per_chunk,H,W,4] with lohi [frames_per_chunk,4,2]")
+    return fpc, H, W, [_chk(c, "chunk", torch.uint16) for c in chunks], [_chk(l, "lohi chunk") for l in lohi_chunks]
+
+
+def _slot_addresses(slots, chunk_ptrs, lohi_ptrs, frames_per_chunk, frame_bytes):
+    """Slot s is frame s % frames_per_chunk of chunk s // frames_per_chunk: int64 slots, all of the store -> (packed addresses,
+    lohi addresses)."""
+    chunk, within = slots // frames_per_chunk, slots % frames_per_chunk
+    return np.asarray(chunk_ptrs, dtype=np.int64)[chunk] + within * frame_bytes, np.asarray(lohi_ptrs, dtype=np.int64)[chunk] + within * 32
+
+
+def trackstore_slot_addresses(chunks, lohi_chunks, slots):
+    """The device addresses of stored frames: chunks / lohi_chunks as for ``trackstore_query``; slots: HOST integers, -1 for
+    "no frame" -> (packed addresses, lohi addresses) as int64 arrays of the slots' shape, 0 where the slot is -1."""
+    fpc, H, W, cptr, lptr = _trackstore_chunks(chunks, lohi_chunks, "trackstore_slot_addresses")
+    slots = np.asarray(slots, dtype=np.int64)
+    if slots.size and (slots.min() < -1 or slots.max() >= fpc * len(cptr)):
+        raise MftxError("trackstore_slot_addresses: slots must be slots of the store, or -1")
+    held = slots >= 0
+    packed, lohi = _slot_addresses(np.where(held, slots, 0), cptr, lptr, fpc, H * W * 8)
+    return np.where(held, packed, 0), np.where(held, lohi, 0)
+
+
+def _pack_tables(int64_parts, int32_parts):
+    """Host tables (1-D arrays) laid out for one upload -> (ONE int64 array: the int64 parts, then the int32 parts in its tail, so
+    that pointer tables sit at multiples of 8 bytes and the others at multiples of 4; the byte offset of each part, in the order
+    given)."""
+    n64, n32 = sum(map(len, int64_parts)), sum(map(len, int32_parts))
+    buf = np.zeros(n64 + (n32 + 1) // 2, np.int64)
+    tail = buf[n64:].view(np.int32)
+    offsets, at = [], 0
+    for part in int64_parts:
+        buf[at:at + len(part)] = part
+        offsets.append(8 * at)
+        at += len(part)
+    at = 0
+    for part in int32_parts:
+        tail[at:at + len(part)] = part
+        offsets.append(8 * n64 + 4 * at)
+        at += len(part)
+    return buf, tuple(offsets)
+
+
+def _upload_tables(device, int64_parts, int32_parts):
+    """``_pack_tables``, sent up through pinned memory without a host synchronisation -> (the device tensor, which the caller keeps
+    alive until its call is enqueued; each part's device address)."""
+    buf, offsets = _pack_tables(int64_parts, int32_parts)
+    tables = torch.from_numpy(buf).pin_memory().to(device, non_blocking=True)
+    return tables, tuple(tables.data_ptr() + o for o in offsets)
+
+
 def trackstore_query(chunks, lohi_chunks, slots, xy, table, column0=0):
     """Point read-out of stored frames in one call (``mftx_trackstore_query``).  chunks: uint16 device tensors
     [frames_per_chunk, H, W, 4] with lohi_chunks float32 [frames_per_chunk, 4, 2] beside them (slot s = frame
@@ -1024,26 +1084,33 @@ def trackstore_query(chunks, lohi_chunks, slots, xy, table, column0=0):
     sigma) of point i on the frame in slots[j] -- bitwise ``sample_points`` on that frame's ``trackstore_unpack``-ed planes;
     nothing else of the table is touched.  Returns ``table``."""
     lib = _lib.load()
-    chunks, lohi_chunks = list(chunks), list(lohi_chunks)
-    if not chunks or len(chunks) != len(lohi_chunks):
-        raise MftxError("trackstore_query: as many lohi tables as chunks, at least one")
-    fpc, H, W = (int(s) for s in chunks[0].shape[:3])
-    for c, l in zip(chunks, lohi_chunks):
-        if tuple(c.shape) != (fpc, H, W, 4) or tuple(l.shape) != (fpc, 4, 2):
-            raise MftxError("trackstore_query: chunks must be [frames_per_chunk,H,W,4] with lohi [frames_per_chunk,4,2]")
+    fpc, H, W, cptr, lptr = _trackstore_chunks(chunks, lohi_chunks, "trackstore_query")
     if xy.dim() != 2 or int(xy.shape[1]) != 2 or slots.dim() != 1:
         raise MftxError("trackstore_query: slots must be [T], xy [N, 2]")
     N, T = int(xy.shape[0]), int(slots.shape[0])
     if table.dim() != 3 or int(table.shape[0]) != N or int(table.shape[2]) != 4:
         raise MftxError("trackstore_query: the table must be [N, frames, 4]")
-    carr = _lib.ptr_array([_chk(c, "chunk", torch.uint16) for c in chunks])
-    larr = _lib.ptr_array([_chk(l, "lohi chunk") for l in lohi_chunks])
+    carr, larr = _lib.ptr_array(cptr), _lib.ptr_array(lptr)
     if N == 0 or T == 0:          # (empty tensors have no storage to point at)
         return table
-    check(lib.mftx_trackstore_query(carr[0], larr[0], len(chunks), fpc, _chk(slots, "slots", torch.int32), T, H, W, N,
+    check(lib.mftx_trackstore_query(carr[0], larr[0], len(cptr), fpc, _chk(slots, "slots", torch.int32), T, H, W, N,
                                     _chk(xy, "xy"), _chk(table, "table"), 4 * int(table.shape[1]), int(column0), _stream()),
           "mftx_trackstore_query")
     return table
+
+
+def _locate_parts(point_slots, chunk_ptrs, lohi_ptrs, frames_per_chunk, frame_bytes):
+    """-> (G, (frames, lohis), (group_start, order, group_of)): the tables of ``locate_tables`` before they are laid out."""
+    slots = np.asarray(point_slots, dtype=np.int64).reshape(-1)
+    N = int(slots.shape[0])
+    order = np.argsort(slots, kind="stable")
+    sorted_slots = slots[order]
+    first = np.flatnonzero(np.concatenate([[True], sorted_slots[1:] != sorted_slots[:-1]]))
+    G = int(first.shape[0])
+    group_start = np.concatenate([first, [N]])
+    group_of = np.empty(N, np.int32)
+    group_of[order] = np.repeat(np.arange(G, dtype=np.int32), np.diff(group_start))
+    return G, _slot_addresses(sorted_slots[first], chunk_ptrs, lohi_ptrs, frames_per_chunk, frame_bytes), (group_start, order, group_of)
 
 
 def locate_tables(point_slots, chunk_ptrs, lohi_ptrs, frames_per_chunk, frame_bytes):
@@ -1051,26 +1118,31 @@ def locate_tables(point_slots, chunk_ptrs, lohi_ptrs, frames_per_chunk, frame_by
     order) as ONE int64 host array, and where its parts begin: -> (buf, G, (frames, lohis, group_start, order, group_of) byte
     offsets).  Queries are grouped by slot (stable, slots ascending): frames / lohis [G] addresses (``chunk_ptrs[c]`` +
     the frame's offset in its chunk), then int32 group_start [G + 1], order [N], group_of [N]."""
+    G, int64_parts, int32_parts = _locate_parts(point_slots, chunk_ptrs, lohi_ptrs, frames_per_chunk, frame_bytes)
+    buf, offsets = _pack_tables(int64_parts, int32_parts)
+    return buf, G, offsets
+
+
+def _locate_call(name, slots_what, H, W, chunk_ptrs, lohi_ptrs, frames_per_chunk, point_slots, xy, table, cell, occlusion_threshold):
+    """``mftx_trackstore_locate`` over the frames ``_slot_addresses`` finds in the slots ``point_slots``."""
+    lib = _lib.load()
+    if xy.dim() != 2 or int(xy.shape[1]) != 2:
+        raise MftxError(f"{name}: xy must be [N, 2]")
+    N = int(xy.shape[0])
     slots = np.asarray(point_slots, dtype=np.int64).reshape(-1)
-    N = int(slots.shape[0])
-    order = np.argsort(slots, kind="stable")
-    sorted_slots = slots[order]
-    first = np.flatnonzero(np.concatenate([[True], sorted_slots[1:] != sorted_slots[:-1]]))
-    G = int(first.shape[0])
-    group_slot = sorted_slots[first]
-    group_of = np.empty(N, np.int32)
-    group_of[order] = np.repeat(np.arange(G, dtype=np.int32), np.diff(np.concatenate([first, [N]])))
-    chunk, within = group_slot // frames_per_chunk, group_slot % frames_per_chunk
-    n32 = (G + 1) + 2 * N
-    buf = np.zeros(2 * G + (n32 + 1) // 2, np.int64)
-    buf[0:G] = np.asarray(chunk_ptrs, dtype=np.int64)[chunk] + within * frame_bytes
-    buf[G:2 * G] = np.asarray(lohi_ptrs, dtype=np.int64)[chunk] + within * 32
-    tail = buf[2 * G:].view(np.int32)
-    tail[0:G] = first
-    tail[G] = N
-    tail[G + 1:G + 1 + N] = order
-    tail[G + 1 + N:G + 1 + 2 * N] = group_of
-    return buf, G, (0, 8 * G, 16 * G, 16 * G + 4 * (G + 1), 16 * G + 4 * (G + 1) + 4 * N)
+    if int(slots.shape[0]) != N or (N and (slots.min() < 0 or slots.max() >= frames_per_chunk * len(chunk_ptrs))):
+        raise MftxError(f"{name}: {slots_what}")
+    if tuple(table.shape) != (N, 4) or tuple(cell.shape) != (N,):
+        raise MftxError(f"{name}: the table must be [N, 4], cell [N]")
+    xp, tp, cp = _chk(xy, "xy"), _chk(table, "table"), _chk(cell, "cell", torch.int32)
+    if N == 0:
+        return table, cell
+    G, int64_parts, int32_parts = _locate_parts(slots, chunk_ptrs, lohi_ptrs, frames_per_chunk, H * W * 8)
+    tables, (frames, lohis, group_start, order, group_of) = _upload_tables(xy.device, int64_parts, int32_parts)
+    keys = torch.empty(N, dtype=torch.int64, device=xy.device)
+    check(lib.mftx_trackstore_locate(frames, lohis, group_start, G, order, group_of, H, W, N, xp, float(occlusion_threshold),
+                                     keys.data_ptr(), tp, cp, _stream()), "mftx_trackstore_locate")
+    return table, cell
 
 
 def trackstore_locate(chunks, lohi_chunks, point_slots, xy, table, cell, occlusion_threshold=0.5):
@@ -1080,34 +1152,9 @@ def trackstore_locate(chunks, lohi_chunks, point_slots, xy, table, cell, occlusi
     point (x, y) whose image on that frame is xy[n], and occlusion and sigma there; ``cell`` (int32 device [N]) the template
     cell it lies in, -1 (and a row of NaN) where nothing maps to xy[n].  The group tables go up through one pinned buffer;
     no host synchronisation.  Returns (table, cell)."""
-    lib = _lib.load()
-    chunks, lohi_chunks = list(chunks), list(lohi_chunks)
-    if not chunks or len(chunks) != len(lohi_chunks):
-        raise MftxError("trackstore_locate: as many lohi tables as chunks, at least one")
-    fpc, H, W = (int(s) for s in chunks[0].shape[:3])
-    for c, l in zip(chunks, lohi_chunks):
-        if tuple(c.shape) != (fpc, H, W, 4) or tuple(l.shape) != (fpc, 4, 2):
-            raise MftxError("trackstore_locate: chunks must be [frames_per_chunk,H,W,4] with lohi [frames_per_chunk,4,2]")
-    if xy.dim() != 2 or int(xy.shape[1]) != 2:
-        raise MftxError("trackstore_locate: xy must be [N, 2]")
-    N = int(xy.shape[0])
-    slots = np.asarray(point_slots, dtype=np.int64).reshape(-1)
-    if int(slots.shape[0]) != N or (N and (slots.min() < 0 or slots.max() >= fpc * len(chunks))):
-        raise MftxError("trackstore_locate: point_slots must be N slots of the store")
-    if tuple(table.shape) != (N, 4) or tuple(cell.shape) != (N,):
-        raise MftxError("trackstore_locate: the table must be [N, 4], cell [N]")
-    cptr = [_chk(c, "chunk", torch.uint16) for c in chunks]
-    lptr = [_chk(l, "lohi chunk") for l in lohi_chunks]
-    xp, tp, cp = _chk(xy, "xy"), _chk(table, "table"), _chk(cell, "cell", torch.int32)
-    if N == 0:
-        return table, cell
-    buf, G, off = locate_tables(slots, cptr, lptr, fpc, H * W * 8)
-    tables = torch.from_numpy(buf).pin_memory().to(xy.device, non_blocking=True)
-    keys = torch.empty(N, dtype=torch.int64, device=xy.device)
-    base = tables.data_ptr()
-    check(lib.mftx_trackstore_locate(base + off[0], base + off[1], base + off[2], G, base + off[3], base + off[4], H, W, N, xp,
-                                     float(occlusion_threshold), keys.data_ptr(), tp, cp, _stream()), "mftx_trackstore_locate")
-    return table, cell
+    fpc, H, W, cptr, lptr = _trackstore_chunks(chunks, lohi_chunks, "trackstore_locate")
+    return _locate_call("trackstore_locate", "point_slots must be N slots of the store", H, W, cptr, lptr, fpc, point_slots, xy,
+                        table, cell, occlusion_threshold)
 
 
 def trackstore_invert(chunks, lohi_chunks, slots, table, cell, occlusion_threshold=0.5):
@@ -1118,30 +1165,19 @@ def trackstore_invert(chunks, lohi_chunks, slots, table, cell, occlusion_thresho
     device [G,H,W]) the template cell, -1 (and a row of NaN) where nothing maps to the pixel.  The two pointer tables go up
     through one pinned buffer; no host synchronisation.  Returns (table, cell)."""
     lib = _lib.load()
-    chunks, lohi_chunks = list(chunks), list(lohi_chunks)
-    if not chunks or len(chunks) != len(lohi_chunks):
-        raise MftxError("trackstore_invert: as many lohi tables as chunks, at least one")
-    fpc, H, W = (int(s) for s in chunks[0].shape[:3])
-    for c, l in zip(chunks, lohi_chunks):
-        if tuple(c.shape) != (fpc, H, W, 4) or tuple(l.shape) != (fpc, 4, 2):
-            raise MftxError("trackstore_invert: chunks must be [frames_per_chunk,H,W,4] with lohi [frames_per_chunk,4,2]")
+    fpc, H, W, cptr, lptr = _trackstore_chunks(chunks, lohi_chunks, "trackstore_invert")
     slots = np.asarray(slots, dtype=np.int64).reshape(-1)
     G = int(slots.shape[0])
-    if G and (slots.min() < 0 or slots.max() >= fpc * len(chunks)):
+    if G and (slots.min() < 0 or slots.max() >= fpc * len(cptr)):
         raise MftxError("trackstore_invert: slots must be slots of the store")
     if tuple(table.shape) != (G, H, W, 4) or tuple(cell.shape) != (G, H, W):
         raise MftxError("trackstore_invert: the table must be [G, H, W, 4], cell [G, H, W]")
-    cptr = np.asarray([_chk(c, "chunk", torch.uint16) for c in chunks], dtype=np.int64)
-    lptr = np.asarray([_chk(l, "lohi chunk") for l in lohi_chunks], dtype=np.int64)
     tp, cp = _chk(table, "table"), _chk(cell, "cell", torch.int32)
     if G == 0:
         return table, cell
-    chunk, within = slots // fpc, slots % fpc
-    buf = np.concatenate([cptr[chunk] + within * (H * W * 8), lptr[chunk] + within * 32])
-    tables = torch.from_numpy(buf).pin_memory().to(table.device, non_blocking=True)
+    tables, (frames, lohis) = _upload_tables(table.device, _slot_addresses(slots, cptr, lptr, fpc, H * W * 8), ())
     keys = torch.empty(G * H * W, dtype=torch.int64, device=table.device)
-    base = tables.data_ptr()
-    check(lib.mftx_trackstore_invert(base, base + 8 * G, G, H, W, float(occlusion_threshold), keys.data_ptr(), tp, cp, _stream()),
+    check(lib.mftx_trackstore_invert(frames, lohis, G, H, W, float(occlusion_threshold), keys.data_ptr(), tp, cp, _stream()),
           "mftx_trackstore_invert")
     return table, cell
 
@@ -1161,26 +1197,9 @@ def trackstore_locate_frames(frames, point_frame, xy, table, cell, occlusion_thr
     """``trackstore_locate`` over stored frames of ANY stores, in one call (``mftx_trackstore_locate``): frames = J x (packed
     [H,W,4], lohi [4,2]) device views; point_frame: N HOST integers, the index into ``frames`` of the frame each point is given
     on.  xy, table, cell as for ``trackstore_locate``.  One pinned buffer, no host synchronisation.  Returns (table, cell)."""
-    lib = _lib.load()
     H, W, pptr, lptr = _trackstore_frame_ptrs(frames, "trackstore_locate_frames")
-    if xy.dim() != 2 or int(xy.shape[1]) != 2:
-        raise MftxError("trackstore_locate_frames: xy must be [N, 2]")
-    N = int(xy.shape[0])
-    which = np.asarray(point_frame, dtype=np.int64).reshape(-1)
-    if int(which.shape[0]) != N or (N and (which.min() < 0 or which.max() >= len(pptr))):
-        raise MftxError("trackstore_locate_frames: point_frame must be N indices into frames")
-    if tuple(table.shape) != (N, 4) or tuple(cell.shape) != (N,):
-        raise MftxError("trackstore_locate_frames: the table must be [N, 4], cell [N]")
-    xp, tp, cp = _chk(xy, "xy"), _chk(table, "table"), _chk(cell, "cell", torch.int32)
-    if N == 0:
-        return table, cell
-    buf, G, off = locate_tables(which, pptr, lptr, 1, H * W * 8)         # (every frame a chunk of its own)
-    tables = torch.from_numpy(buf).pin_memory().to(xy.device, non_blocking=True)
-    keys = torch.empty(N, dtype=torch.int64, device=xy.device)
-    base = tables.data_ptr()
-    check(lib.mftx_trackstore_locate(base + off[0], base + off[1], base + off[2], G, base + off[3], base + off[4], H, W, N, xp,
-                                     float(occlusion_threshold), keys.data_ptr(), tp, cp, _stream()), "mftx_trackstore_locate")
-    return table, cell
+    return _locate_call("trackstore_locate_frames", "point_frame must be N indices into frames", H, W, pptr, lptr, 1, point_frame,
+                        xy, table, cell, occlusion_threshold)         # (every frame a chunk of its own)
 
 
 TRACKSTORE_ATLAS_ENTRIES = 256           # entries per plane of mftx_trackstore_invert_atlas (8 bits of its key)
@@ -1219,41 +1238,15 @@ def trackstore_invert_atlas(frames, first_of, rank_of, table, cell, entry, occlu
         pptr = lptr = np.zeros(0, np.int64)
     if G == 0:
         return table, cell, entry
-    n32 = (G + 1) + J
-    buf = np.zeros(2 * J + (n32 + 1) // 2, np.int64)
-    buf[0:J], buf[J:2 * J] = pptr, lptr
-    tail = buf[2 * J:].view(np.int32)
-    tail[0:G + 1], tail[G + 1:G + 1 + J] = first_of, rank_of
-    tables = torch.from_numpy(buf).pin_memory().to(table.device, non_blocking=True)
+    tables, (fr, lh, fo, ro) = _upload_tables(table.device, (pptr, lptr), (first_of, rank_of))
     keys = torch.empty(G * H * W, dtype=torch.int64, device=table.device)
-    base = tables.data_ptr()
-    check(lib.mftx_trackstore_invert_atlas(base if J else None, base + 8 * J if J else None, base + 16 * J,
-                                           base + 16 * J + 4 * (G + 1) if J else None, G, J, H, W, float(occlusion_threshold),
-                                           keys.data_ptr(), tp, cp, ep, _stream()), "mftx_trackstore_invert_atlas")
+    check(lib.mftx_trackstore_invert_atlas(fr if J else None, lh if J else None, fo, ro if J else None, G, J, H, W,
+                                           float(occlusion_threshold), keys.data_ptr(), tp, cp, ep, _stream()),
+          "mftx_trackstore_invert_atlas")
     return table, cell, entry
 
 
 TRACKSTORE_FLOW_COLUMNS = 16             # columns per workgroup of mftx_trackstore_flow_from unless the caller says otherwise
-
-
-def trackstore_slot_addresses(chunks, lohi_chunks, slots):
-    """The device addresses of stored frames: chunks / lohi_chunks as for ``trackstore_query``; slots: HOST integers, -1 for
-    "no frame" -> (packed addresses, lohi addresses) as int64 arrays of the slots' shape, 0 where the slot is -1."""
-    chunks, lohi_chunks = list(chunks), list(lohi_chunks)
-    if not chunks or len(chunks) != len(lohi_chunks):
-        raise MftxError("trackstore_slot_addresses: as many lohi tables as chunks, at least one")
-    fpc, H, W = (int(s) for s in chunks[0].shape[:3])
-    for c, l in zip(chunks, lohi_chunks):
-        if tuple(c.shape) != (fpc, H, W, 4) or tuple(l.shape) != (fpc, 4, 2):
-            raise MftxError("trackstore_slot_addresses: chunks must be [frames_per_chunk,H,W,4] with lohi [frames_per_chunk,4,2]")
-    slots = np.asarray(slots, dtype=np.int64)
-    if slots.size and (slots.min() < -1 or slots.max() >= fpc * len(chunks)):
-        raise MftxError("trackstore_slot_addresses: slots must be slots of the store, or -1")
-    cptr = np.asarray([_chk(c, "chunk", torch.uint16) for c in chunks], dtype=np.int64)
-    lptr = np.asarray([_chk(l, "lohi chunk") for l in lohi_chunks], dtype=np.int64)
-    held = slots >= 0
-    chunk, within = np.where(held, slots // fpc, 0), np.where(held, slots % fpc, 0)
-    return np.where(held, cptr[chunk] + within * (H * W * 8), 0), np.where(held, lptr[chunk] + within * 32, 0)
 
 
 def trackstore_flow_from(table, entry, row_of, frame_ptrs, lohi_ptrs, flow, occl, sigma, columns_per_block=0):
@@ -1284,14 +1277,9 @@ def trackstore_flow_from(table, entry, row_of, frame_ptrs, lohi_ptrs, flow, occl
     fp, op, sp = _chk(flow, "flow"), _chk(occl, "occl"), _chk(sigma, "sigma")
     if T == 0:
         return flow, occl, sigma
-    n = R * T
-    buf = np.zeros(2 * n + (n_ranks + 1) // 2, np.int64)
-    buf[0:n], buf[n:2 * n] = frame_ptrs.reshape(-1), lohi_ptrs.reshape(-1)
-    buf[2 * n:].view(np.int32)[0:n_ranks] = row_of
-    tables = torch.from_numpy(buf).pin_memory().to(table.device, non_blocking=True)
-    base = tables.data_ptr()
-    check(lib.mftx_trackstore_flow_from(tp, ep, base + 16 * n, base, base + 8 * n, n_ranks, R, T, H, W, int(columns_per_block),
-                                        fp, op, sp, _stream()), "mftx_trackstore_flow_from")
+    tables, (frames, lohis, rows) = _upload_tables(table.device, (frame_ptrs.reshape(-1), lohi_ptrs.reshape(-1)), (row_of,))
+    check(lib.mftx_trackstore_flow_from(tp, ep, rows, frames, lohis, n_ranks, R, T, H, W, int(columns_per_block), fp, op, sp,
+                                        _stream()), "mftx_trackstore_flow_from")
     return flow, occl, sigma
 
 

@@ -35,6 +35,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from .trackstore import _as_points, _frame_ids, _tracks_to_host, chain_behind_inverse
+
 MAX_ENTRIES = 256                 # 8 bits of the dense inverse's key
 MAX_CELLS = 1 << 24               # ... and 24 for the cell: (H - 1)(W - 1)
 _NOT_FOUND = torch.iinfo(torch.int64).max
@@ -101,13 +103,6 @@ class TrackAtlas:
         t = torch.from_numpy(np.ascontiguousarray(a))
         return t.pin_memory().to(self.device, non_blocking=True) if self.native else t
 
-    def _points(self, points, name):
-        if not isinstance(points, torch.Tensor):
-            points = torch.from_numpy(np.ascontiguousarray(np.asarray(points, dtype=np.float32)))
-        if points.dim() != 2 or int(points.shape[1]) != 2:
-            raise ValueError(f"TrackAtlas.{name}: points must be (N, 2), not {tuple(points.shape)}")
-        return points.to(device=self.device, dtype=torch.float32).contiguous()
-
     def _reduce(self, tq, cq, ranks, thr):
         """tq [E, n, 4], cq [E, n]: the answers of the entries ``ranks`` (ascending) to n queries -> the winner's (table [n, 4],
         cell [n], entry [n]) by the smallest (occlusion > thr, bits of (sigma > 0 ? sigma : +0), rank) among the entries that
@@ -135,15 +130,13 @@ class TrackAtlas:
         cell, and its rank (``atlas.entries[rank]``).  Where no entry finds the query: entry = cell = -1 and a row of NaN.  A
         frame that no entry holds is a ``KeyError``.  On the device: one kernel call and a reduction, and with ``points`` a
         device tensor no host synchronisation."""
-        xy = self._points(points, "locate")
+        xy = _as_points(points, self.device, "TrackAtlas.locate")
         N = int(xy.shape[0])
-        ids = np.asarray(frame)
-        if ids.ndim == 0:
-            groups = [(int(ids), None)]                                         # (frame, the points given on it: all)
-        elif ids.ndim == 1 and ids.shape[0] == N:
+        ids, lead = _frame_ids(frame, "TrackAtlas.locate", N)
+        if lead:
             groups = [(int(f), np.flatnonzero(ids == f)) for f in np.unique(ids)]
         else:
-            raise ValueError(f"TrackAtlas.locate: frame must be one frame id or {N} of them")
+            groups = [(int(ids[0]), None)]                                      # (frame, the points given on it: all)
         holders = [self._holders(f) for f, _ in groups]                        # KeyError before any work
         table = torch.empty((N, 4), dtype=torch.float32, device=self.device)
         cell = torch.empty((N,), dtype=torch.int32, device=self.device)
@@ -161,7 +154,7 @@ class TrackAtlas:
                     which.append(np.full(n, len(views), np.int64))
                     views.append(self._frame_views(r, f))
                     index.append(np.arange(N) if pts is None else pts)
-            if ids.ndim == 0:
+            if not lead:
                 xq = xy.repeat(len(views), 1)
             else:
                 xq = xy.index_select(0, self._upload(np.concatenate(index).astype(np.int64)))
@@ -196,13 +189,8 @@ class TrackAtlas:
         [G, H, W].  On the device: ONE call whatever G and the number of entries are (``mftx_trackstore_invert_atlas``: all
         entries of a frame scattered onto one key plane, 8 + 28 bytes per pixel and plane of workspace and results instead of that per
         entry), and no host synchronisation."""
-        ids = np.asarray(frame)
-        if ids.ndim == 0:
-            fs, lead = [int(ids)], ()
-        elif ids.ndim == 1:
-            fs, lead = [int(f) for f in ids], (int(ids.shape[0]),)
-        else:
-            raise ValueError("TrackAtlas.inverse: frame must be one frame id or a sequence of them")
+        ids, lead = _frame_ids(frame, "TrackAtlas.inverse")
+        fs = [int(f) for f in ids]
         holders = [self._holders(f) for f in fs]                               # KeyError before any work
         H, W, G = self.H, self.W, len(fs)
         table = torch.empty((G, H, W, 4), dtype=torch.float32, device=self.device)
@@ -236,7 +224,7 @@ class TrackAtlas:
         holds the frame -- which joins a forward and a backward store of one template -- and a row of NaN for a frame that no
         entry of the template holds.  ``KeyError`` for a template frame without an entry.  No host synchronisation."""
         frames, owner = self._columns(template_frame, frames)
-        xy = self._points(points, "query")
+        xy = _as_points(points, self.device, "TrackAtlas.query")
         N, T = int(xy.shape[0]), len(frames)
         out = torch.full((N, T, 4), float("nan"), dtype=torch.float32, device=self.device)
         if N == 0:
@@ -273,8 +261,8 @@ class TrackAtlas:
             covered[s] = np.asarray(self._columns(s, cols)[1]) >= 0
             if N and T:
                 tracks = torch.where((template == s)[:, None, None], self.query(s, at, cols), tracks)
-        both = torch.cat([tracks.reshape(N, T * 4), template.to(torch.float32)[:, None]], dim=1).cpu().numpy()
-        tracks, template = both[:, :T * 4].reshape(N, T, 4), both[:, T * 4].astype(np.int64)
+        tracks, template = _tracks_to_host(tracks, template)
+        template = template.astype(np.int64)
         found = template >= 0
         coords, occl = tracks[:, :, 0:2].copy(), tracks[:, :, 2].copy()
         lost = np.ones((N, T), bool)
@@ -331,16 +319,8 @@ class TrackAtlas:
             if T and cov.any():
                 q = torch.where(mine[:, None, None], self.query(s, at, cols), q)
                 ok = torch.where(mine[:, None], self._upload(cov)[None, :], ok)
-        grid = self.entries[0][1]._pixel_grid()
-        flow = q[:, :, 0:2] - grid[:, None, :]
-        occl = torch.maximum(tb[:, None, 2], q[:, :, 2])
-        s_src, s_dst = tb[:, None, 3], q[:, :, 3]
-        # (the root taken in float64 and rounded once, as DenseTrackStore.results_from takes it)
-        sigma = torch.sqrt((s_src * s_src + s_dst * s_dst).to(torch.float64)).to(torch.float32)
-        flow = torch.where(ok[:, :, None], flow, torch.full((), float("nan"), dtype=torch.float32, device=self.device))
-        occl = torch.where(ok, occl, torch.ones((), dtype=torch.float32, device=self.device))
-        sigma = torch.where(ok, sigma, torch.full((), float("inf"), dtype=torch.float32, device=self.device))
-        return flow.permute(1, 2, 0).reshape(T, 2, H, W), occl.t().reshape(T, 1, H, W), sigma.t().reshape(T, 1, H, W)
+        flow, occl, sigma = chain_behind_inverse(tb, q, self.entries[0][1]._pixel_grid(), ok)
+        return flow.reshape(T, 2, H, W), occl.reshape(T, 1, H, W), sigma.reshape(T, 1, H, W)
 
     def results_from(self, src, frames=None, occlusion_threshold=0.5, out=None):
         """The dense results FROM video frame ``src`` to ``frames`` (default: ``atlas.frames``), every pixel followed on the template

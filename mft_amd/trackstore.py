@@ -129,6 +129,56 @@ def _locate_host(planes, q, thr, table, cell):
         cell[n] = idx[w]
 
 
+def _as_points(points, device, name=None):
+    """points: anything (N, 2)-like -> float32 [N, 2] on ``device``, contiguous.  With ``name`` (of the method asking) any other
+    shape is a ``ValueError``; without it the points are reshaped to (-1, 2)."""
+    if not isinstance(points, torch.Tensor):
+        points = torch.from_numpy(np.ascontiguousarray(np.asarray(points, dtype=np.float32)))
+    if name is None:
+        points = points.reshape(-1, 2)
+    elif points.dim() != 2 or int(points.shape[1]) != 2:
+        raise ValueError(f"{name}: points must be (N, 2), not {tuple(points.shape)}")
+    return points.to(device=device, dtype=torch.float32).contiguous()
+
+
+def _frame_ids(frame, name, n=None):
+    """``frame``: one frame id, or a host sequence of them (of exactly ``n`` where ``n`` is given) -> (ids: a 1-D array, lead: () for
+    the single id, (len(ids),) for a sequence).  Anything else is a ``ValueError``."""
+    ids = np.asarray(frame)
+    if ids.ndim == 0:
+        return ids.reshape(1), ()
+    if ids.ndim == 1 and (n is None or ids.shape[0] == n):
+        return ids, (int(ids.shape[0]),)
+    raise ValueError(f"{name}: frame must be one frame id or " + ("a sequence of them" if n is None else f"{n} of them"))
+
+
+def _tracks_to_host(tracks, extra):
+    """tracks [N, T, 4] and ``extra`` [N] on the device -> numpy (tracks [N, T, 4], extra [N] as float32) in ONE download."""
+    N, T = int(tracks.shape[0]), int(tracks.shape[1])
+    both = torch.cat([tracks.reshape(N, T * 4), extra.to(torch.float32)[:, None]], dim=1).cpu().numpy()
+    return both[:, :T * 4].reshape(N, T, 4), both[:, T * 4]
+
+
+def chain_behind_inverse(table, q, grid, ok):
+    """The rule by which results are chained (MFT/MFT.py:233-239) with an inverse as the left result: table [N, 4] = the inverse's
+    (Px, Py, o_src, s_src) per pixel, q [N, T, 4] = the read-out (qx, qy, o_dst, s_dst) of that point per column, grid [N, 2] the
+    pixels' centres, ok [N] or [N, T] bool -> planar (flow [T, 2, N], occlusion [T, N], sigma [T, N]): flow = q - pixel,
+    occlusion = max(o_src, o_dst), sigma = sqrt(s_src^2 + s_dst^2), and NaN, 1, +inf where not ok."""
+    flow = q[:, :, 0:2] - grid[:, None, :]
+    occl = torch.maximum(table[:, None, 2], q[:, :, 2])
+    s_src, s_dst = table[:, None, 3], q[:, :, 3]
+    # (the root taken in float64 and rounded once: the correctly rounded float32 root on every device -- torch's own float32
+    # sqrt is an ulp off numpy's for some arguments on the host)
+    sigma = torch.sqrt((s_src * s_src + s_dst * s_dst).to(torch.float64)).to(torch.float32)
+    if ok.dim() == 1:
+        ok = ok[:, None]
+    nan, one, inf = (torch.full((), v, dtype=torch.float32, device=q.device) for v in (float("nan"), 1.0, float("inf")))
+    flow = torch.where(ok[:, :, None], flow, nan)            # (each name rebound at once: no second copy of a plane stays alive)
+    occl = torch.where(ok, occl, one)
+    sigma = torch.where(ok, sigma, inf)
+    return flow.permute(1, 2, 0), occl.t(), sigma.t()
+
+
 class DenseTrackStore:
     def __init__(self, H, W, device="cuda", frames_per_chunk=64, max_bytes=None):
         """A store of H x W frames.  Storage grows by chunks of ``frames_per_chunk`` frames (torch allocations on ``device``);
@@ -262,9 +312,7 @@ class DenseTrackStore:
         ``warp_forward_points`` and ``sample`` of the results API on the dequantised frames.  ``out``: a [N, T, 4] tensor to
         write into.  On the device: one kernel call, and with ``points`` a device tensor no host synchronisation."""
         slots = self._slots(frames)
-        if not isinstance(points, torch.Tensor):
-            points = torch.from_numpy(np.ascontiguousarray(np.asarray(points, dtype=np.float32)))
-        xy = points.to(device=self.device, dtype=torch.float32).reshape(-1, 2).contiguous()
+        xy = _as_points(points, self.device)
         N, T = int(xy.shape[0]), len(slots)
         if out is None:
             out = torch.zeros((N, T, 4), dtype=torch.float32, device=self.device)
@@ -314,19 +362,10 @@ class DenseTrackStore:
         template points map to the query the one that is not occluded (occlusion <= ``occlusion_threshold``), then of lowest
         sigma, then of lowest cell wins; where none does, cell is -1 and the row is NaN.  ``out``: a (table, cell) pair to
         write into.  On the device: one call, and with ``points`` a device tensor no host synchronisation."""
-        if not isinstance(points, torch.Tensor):
-            points = torch.from_numpy(np.ascontiguousarray(np.asarray(points, dtype=np.float32)))
-        if points.dim() != 2 or int(points.shape[1]) != 2:
-            raise ValueError(f"DenseTrackStore.locate: points must be (N, 2), not {tuple(points.shape)}")
-        xy = points.to(device=self.device, dtype=torch.float32).contiguous()
+        xy = _as_points(points, self.device, "DenseTrackStore.locate")
         N = int(xy.shape[0])
-        ids = np.asarray(frame)
-        if ids.ndim == 0:
-            slots = [self.slot_of(ids)] * N                    # KeyError for a frame that was never appended
-        elif ids.ndim == 1 and ids.shape[0] == N:
-            slots = [self.slot_of(f) for f in ids]
-        else:
-            raise ValueError(f"DenseTrackStore.locate: frame must be one frame id or {N} of them")
+        ids, lead = _frame_ids(frame, "DenseTrackStore.locate", N)
+        slots = [self.slot_of(f) for f in ids] * (1 if lead else N)      # KeyError for a frame that was never appended
         if out is None:
             out = (torch.empty((N, 4), dtype=torch.float32, device=self.device), torch.empty((N,), dtype=torch.int32, device=self.device))
         table, cell = out
@@ -358,10 +397,8 @@ class DenseTrackStore:
         table, cell = self.locate(points, frame, occlusion_threshold)
         found = cell >= 0
         template = torch.where(found[:, None], table[:, 0:2], torch.zeros((), dtype=torch.float32, device=self.device))
-        tracks = self.query(template, frames)
-        N, T = int(tracks.shape[0]), int(tracks.shape[1])
-        both = torch.cat([tracks.reshape(N, T * 4), found.to(torch.float32)[:, None]], dim=1).cpu().numpy()
-        tracks, found = both[:, :T * 4].reshape(N, T, 4), both[:, T * 4] > 0
+        tracks, found = _tracks_to_host(self.query(template, frames), found)
+        found = found > 0
         coords, occl = tracks[:, :, 0:2].copy(), tracks[:, :, 2].copy()
         coords[~found], occl[~found] = np.nan, 1.0
         return coords, occl, found
@@ -378,14 +415,10 @@ class DenseTrackStore:
         sigma) of the template point whose image is pixel (x, y) of that frame, cell[y, x] its template cell, -1 (and a row of
         NaN) where nothing maps to the pixel.  A sequence of G frame ids gives [G, H, W, 4] and [G, H, W].  ``out``: a
         (table, cell) pair to write into.  On the device: ONE call whatever G is -- every template cell writes itself onto the
-        pixels its image covers (csrc/trackstore.hip, ts_invert_scatter_kernel) -- and no host synchronisation."""
-        ids = np.asarray(frame)
-        if ids.ndim == 0:
-            slots, lead = [self.slot_of(ids)], ()              # KeyError for a frame that was never appended
-        elif ids.ndim == 1:
-            slots, lead = [self.slot_of(f) for f in ids], (int(ids.shape[0]),)
-        else:
-            raise ValueError("DenseTrackStore.inverse: frame must be one frame id or a sequence of them")
+        pixels its image covers (csrc/trackstore.hip, ts_atlas_scatter_kernel in its identity mode) -- and no host
+        synchronisation."""
+        ids, lead = _frame_ids(frame, "DenseTrackStore.inverse")
+        slots = [self.slot_of(f) for f in ids]                  # KeyError for a frame that was never appended
         H, W = self.H, self.W
         if out is None:
             out = (torch.empty(lead + (H, W, 4), dtype=torch.float32, device=self.device),
@@ -424,18 +457,8 @@ class DenseTrackStore:
         template = torch.where(found[:, None], table[:, 0:2], zero)
         q = self.query(template, [self.frame_ids[s] for s in slots])                     # [H * W, T, 4]
         T = int(q.shape[1])
-        flow = q[:, :, 0:2] - self._pixel_grid()[:, None, :]
-        occl = torch.maximum(table[:, None, 2], q[:, :, 2])
-        s_src, s_dst = table[:, None, 3], q[:, :, 3]
-        # (the root taken in float64 and rounded once: the correctly rounded float32 root on every device -- torch's own float32
-        # sqrt is an ulp off numpy's for some arguments on the host)
-        sigma = torch.sqrt((s_src * s_src + s_dst * s_dst).to(torch.float64)).to(torch.float32)
-        f = found[:, None]
-        flow = torch.where(f[:, :, None], flow, torch.full((), float("nan"), dtype=torch.float32, device=self.device))
-        occl = torch.where(f, occl, torch.ones((), dtype=torch.float32, device=self.device))
-        sigma = torch.where(f, sigma, torch.full((), float("inf"), dtype=torch.float32, device=self.device))
-        return (flow.permute(1, 2, 0).reshape(T, 2, H, W), occl.t().reshape(T, 1, H, W), sigma.t().reshape(T, 1, H, W),
-                found.view(H, W))
+        flow, occl, sigma = chain_behind_inverse(table, q, self._pixel_grid(), found)
+        return flow.reshape(T, 2, H, W), occl.reshape(T, 1, H, W), sigma.reshape(T, 1, H, W), found.view(H, W)
 
     def result_from(self, src, dst, occlusion_threshold=0.5):
         """-> (``FlowOUTrackingResult`` of the flow from stored frame ``src`` to stored frame ``dst``, found [H, W] bool): one

@@ -217,6 +217,26 @@ def test_invert_atlas_is_per_entry_invert_plus_the_key_minimum(H, W, layout):
         assert lost.sum() > 0 and (e[lost] != 10).all() and (e[(c3 >= 0) & (o3 <= 0.5)] == 10).all() and (e == 10).sum() > 0
 
 
+@pytest.mark.parametrize("H,W", [(9, 34), (24, 40)])
+def test_invert_is_invert_atlas_with_one_entry_per_plane_bytewise(H, W):
+    """``mftx_trackstore_invert`` and ``mftx_trackstore_invert_atlas`` launch the same two kernels, the first in their identity
+    mode (no first_of: plane g is frame g, the key's low word all cell), the second with first_of = [0, 1, 2, 3]: one mode
+    pinned against the other on G = 3 frames.  At 9 x 34 the 33 cell columns make two ragged tile columns; entry 0 has the torn
+    cell that the whole wave walks."""
+    from mft_amd import ops
+    st = case_stores(H, W, 1, DEV)[0]
+    slots = [st.slot_of(f) for f in (1, 2, 0)]
+    table = torch.full((3, H, W, 4), -7.0, device=DEV)
+    cell = torch.full((3, H, W), -77, dtype=torch.int32, device=DEV)
+    ops.trackstore_invert(st._chunks, st._lohi, slots, table, cell)
+    a_table, a_cell, a_entry = torch.full_like(table, -9.0), torch.full_like(cell, -99), torch.full_like(cell, -99)
+    ops.trackstore_invert_atlas([(st.packed(s), st.lohi(s)) for s in slots], [0, 1, 2, 3], [0, 0, 0], a_table, a_cell, a_entry)
+    assert torch.equal(bits(table), bits(a_table))
+    assert torch.equal(cell.cpu(), a_cell.cpu())
+    assert torch.equal(a_entry.cpu(), torch.where(cell >= 0, 0, -1).to(torch.int32).cpu())
+    assert (cell >= 0).any()
+
+
 @pytest.mark.parametrize("n", [1, 2, 5])
 @pytest.mark.parametrize("H,W", [(2, 2), (9, 34), (24, 40)])
 def test_atlas_inverse_locate_and_the_host_atlas_agree_bitwise(H, W, n):

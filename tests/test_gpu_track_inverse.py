@@ -1,5 +1,5 @@
-"""``DenseTrackStore.inverse`` / ``results_from`` on the device (csrc/trackstore.hip: ts_invert_scatter_kernel,
-ts_invert_resolve_kernel through ``ops.trackstore_invert``) against the host restatement (mft_amd/trackstore.py, device="cpu":
+"""``DenseTrackStore.inverse`` / ``results_from`` on the device (csrc/trackstore.hip: ts_atlas_scatter_kernel,
+ts_atlas_resolve_kernel in their identity mode through ``ops.trackstore_invert``) against the host restatement (mft_amd/trackstore.py, device="cpu":
 ``locate`` at every pixel centre), bit for bit; the fields are those of tests/test_track_locate.py and tests/test_track_inverse.py."""
 import functools
 
