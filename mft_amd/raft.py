@@ -352,7 +352,12 @@ class RAFTWrapper:
         ring = self._staging.get(key)
         if ring is None:
             if len(self._staging) >= 4:           # a plugin fed many different sizes: keep the pinned footprint bounded
-                self._staging.pop(next(iter(self._staging)))
+                # The dropped ring's buffers go back to torch's pinned pool, which knows nothing of the copy KERNELS that read them
+                # (it records torch's own copies only): the next user of the pool may write into a block whose upload is still
+                # queued.  So the uploads of a dropped ring complete first (a rare path: the fifth frame shape of a plugin).
+                for slot in self._staging.pop(next(iter(self._staging)))["slots"]:
+                    if slot[1] is not None:
+                        slot[1].synchronize()
             ring = self._staging[key] = {"n": 0, "slots": []}
         if len(ring["slots"]) < self.STAGING_SLOTS:
             buf = torch.empty(key, dtype=torch.uint8).pin_memory()

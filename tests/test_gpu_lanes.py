@@ -10,21 +10,8 @@ pytestmark = pytest.mark.gpu
 
 
 def _tracker(weights_np, lanes, iters, deltas, async_encode=True):
-    from mft_amd.config import Config
-    from mft_amd.MFT import MFT
-    from mft_amd.raft import RAFTWrapper
-    c = Config()
-    c.flow_iters = iters
-    c.async_encode = async_encode
-    c.frames_in_flight = lanes
-    fl = RAFTWrapper(c, state_dict=weights_np)
-    t = Config()
-    t.deltas = list(deltas)
-    t.occlusion_threshold = 0.02
-    t.keep_result_on_device = True
-    t.flow_config = Config()
-    t.flow_config.of_class = lambda cfg: fl
-    return MFT(t), fl
+    from tracker_helpers import make_tracker
+    return make_tracker(weights_np, lanes, iters, deltas, async_encode=async_encode)
 
 
 def _run(tr, vid, n, cache=None, on_device=True):
