@@ -716,6 +716,33 @@ int mftx_trackstore_flow_from(const float *table, const int *entry, const int *r
                               const float *const *lohis, int n_ranks, int R, int T, int H, int W, int columns_per_block,
                               float *flow, float *occl, float *sigma, void *stream);
 
+/* The same results with the template chosen per (pixel, column) among ALL E entries that hold the source frame (its candidates,
+ * ascending rank), instead of once per pixel.  DEVICE memory throughout:
+ *   tables [E][H][W][4] float32 (16-byte aligned) and cells [E][H][W] int32: candidate k's OWN dense inverse of the source frame
+ *   (mftx_trackstore_invert of its stored frame; mftx_trackstore_invert_atlas with one entry per plane gives the same bits) -- its
+ *   template point (Px, Py), occlusion and sigma there, and the cell, < 0 = this candidate does not find the pixel;
+ *   rank_of [E] int32: candidate -> rank (0 .. 255), what `entry` reports; row_of [E] int32: candidate -> row of the pointer tables;
+ *   frames [R * T] / lohis [R * T]: as for mftx_trackstore_flow_from, NULL = that row's template does not cover the column;
+ *   flow [T][2][H][W], occl [T][H][W], sigma [T][H][W] float32 and entry [T][H][W] int32: the results.
+ * Candidate k has an answer for pixel p and column t iff cells[k][p] >= 0, 0 <= row_of[k] < R and the pointers of (row_of[k], t)
+ * are not NULL: the chained result of mftx_trackstore_flow_from, bit for bit, from ITS row of tables.  Among the candidates that
+ * have one the smallest 64-bit key wins,
+ *   key = (occluded << 39) | (sigma field << 8) | rank,   occluded = !(occl <= occlusion_threshold),
+ *   sigma field = 0x7fffffff for a NaN sigma, the float32 bits of sigma where sigma > 0, 0 otherwise,
+ * computed from the CHAINED occl and sigma: visible before occluded, then the lowest chained sigma, then the lowest rank.  This is
+ * NOT the key of mftx_trackstore_locate / _invert_atlas in two respects: a NaN occlusion counts as occluded, and a NaN sigma sorts
+ * behind every number, +inf included -- in a choice among alternatives a NaN never beats a number.  The winner's flow, occl and
+ * sigma are written and its rank to `entry`; where no candidate has an answer: flow NaN (0x7fc00000), occl 1, sigma +inf, entry -1.
+ * ONE launch: pixel blocks of 256 x column blocks of columns_per_block columns (0: the default, 16), a lane per pixel; per group
+ * of 4 columns the candidates are walked in order with the running minimum in registers (a 64-bit integer compare, no atomics),
+ * and every output word is written exactly once.  The results do not depend on columns_per_block.  No allocation, no copy, no
+ * synchronisation.  MFTX_E_ARG: E > 256, H * W >= 2^31, more than 65535 column blocks; MFTX_E_ALIGN: a misaligned table.
+ * T == 0: nothing is done, 0 is returned.  E == 0: every result is the fill, and tables .. lohis are not looked at. */
+int mftx_trackstore_flow_from_best(const float *tables, const int *cells, const int *rank_of, const int *row_of,
+                                   const uint16_t *const *frames, const float *const *lohis, int E, int R, int T, int H, int W,
+                                   float occlusion_threshold, int columns_per_block, float *flow, float *occl, float *sigma,
+                                   int *entry, void *stream);
+
 /* ---- 8f-4: frame / result transport without copy queues -------------------------------------------------------------------
  * A copy KERNEL: src -> dst, n bytes, both 16-byte aligned; either may be PINNED HOST memory (hipHostMalloc / torch
  * pin_memory: mapped into the device's address space), which a kernel reads and writes over PCIe directly.  Unlike

@@ -17,6 +17,8 @@
 //            is these two kernels in their identity mode (one entry per plane, all 32 bits of the key's low word the cell).
 //   flow_from : a plane of the atlas's inverse followed over T columns, each pixel on its winner's template -- query's sampler and
 //            the chaining rule of DenseTrackStore.results_from in one launch, straight to planar flow, occlusion and sigma.
+//   flow_from_best : the same with every entry that holds the source frame a candidate: per (pixel, column) the candidate whose
+//            chained result has the smallest (occluded, sigma, rank) wins -- a 64-bit integer minimum in registers, one launch.
 //
 // Shared between them: TsSampler (query, flow_from: the bilinear sampler set up once per point, its taps' loads and their
 // weighted sum), ts_cell_tile (locate's search, the scatter: a tile's corners staged and the lane's InvCell), ts_solve_cell /
@@ -653,6 +655,108 @@ __global__ __launch_bounds__(256) void ts_flow_from_kernel(const float4 *__restr
     }
 }
 
+// ---- flow_from_best: the template chosen per (pixel, column) among ALL entries that hold the source frame -----------------------------
+// ts_flow_from_kernel follows each pixel on the ONE entry that won the source frame's inverse.  Here every candidate k = 0 .. E - 1
+// (the entries that hold the source frame, ascending rank) brings its OWN inverse plane -- tables[k], cells[k]: per-entry invert --
+// and for every column the candidate whose CHAINED result is best wins:
+//   key = (occluded << 39) | (sigma field << 8) | rank,  occluded = !(occlusion <= thr),
+//   sigma field = 0x7fffffff for a NaN sigma, the bits of sigma where sigma > 0, 0 otherwise,
+// the smallest key: visible before occluded, then the lowest chained sigma, then the lowest rank.  Not ts_locate_key in two respects:
+// a NaN occlusion counts as occluded and a NaN sigma sorts behind every number, +inf included -- among alternatives a NaN never
+// beats a number.  A candidate has a key for a pixel-column iff it found the pixel (cell >= 0) and its template covers the column.
+// A lane owns a pixel, lanes along x, as in ts_flow_from_kernel; but the candidate list is the same for every pixel, so row_of[k],
+// rank_of[k] and the frame and lohi pointers of (candidate, column) are wave-uniform (scalar loads) and only cells[k][p] and
+// tables[k][p] are per lane.  Loop order: column groups of TF_FW outside, candidates inside.  The running best of a group -- key and
+// four values per column -- stays in registers whatever the workgroup's column count is, the sampler is set up again per
+// (candidate, group) from the candidate's row (16 bytes, out of the cache after the first group), and the TF_FW columns' taps of a
+// candidate are all in flight.  The comparison is a 64-bit integer compare in registers: no atomics, no LDS, and each of the five
+// output planes is written once per pixel-column, in contiguous 256-byte runs per wave.
+// Grid: pixel blocks x column blocks of `cols` columns -- ONE launch.
+constexpr int TFB_COLS = 16;        // columns per workgroup unless the caller says otherwise
+constexpr int TFB_ENTRIES = 256;    // candidates (8 bits of the key)
+
+__global__ __launch_bounds__(256) void ts_flow_best_kernel(const float4 *__restrict__ tables, const int *__restrict__ cells,
+                                                           const int *__restrict__ rank_of, const int *__restrict__ row_of,
+                                                           const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
+                                                           int E, int R, int T, int cols, int H, int W, float sx, float sy, float thr,
+                                                           float *__restrict__ flow, float *__restrict__ occl, float *__restrict__ sigma,
+                                                           int *__restrict__ entry) {
+    const long long n = (long long)H * W;
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const long long first = (long long)blockIdx.y * cols;
+    if (first >= T) return;
+    const int t0 = (int)first, t1 = (int)(first + cols < T ? first + cols : T);
+    const float x = (float)(int)(p % W), y = (float)(int)(p / W);
+    const float nan = __uint_as_float(0x7fc00000u), inf = __uint_as_float(0x7f800000u);
+    for (int t = t0; t < t1; t += TF_FW) {
+        unsigned long long best[TF_FW];
+        float bx[TF_FW], by[TF_FW], bo[TF_FW], bs[TF_FW];
+#pragma unroll
+        for (int u = 0; u < TF_FW; ++u) { best[u] = TL_NONE; bx[u] = nan; by[u] = nan; bo[u] = 1.f; bs[u] = inf; }
+        for (int k = 0; k < E; ++k) {
+            // wave-uniform: the candidate's row, rank and its columns' frames
+            const int row = row_of[k];
+            if (row < 0 || row >= R) continue;            // (a table that is not what it should be reads nothing)
+            const unsigned long long rank = (unsigned long long)(rank_of[k] & 0xff);
+            const long long tb = (long long)row * T;
+            const uint2 *frame[TF_FW];
+            const float *lh[TF_FW];
+            bool ok[TF_FW], any = false;
+#pragma unroll
+            for (int u = 0; u < TF_FW; ++u) {
+                frame[u] = nullptr; lh[u] = nullptr;
+                if (t + u < t1) { frame[u] = frames[tb + t + u]; lh[u] = lohis[tb + t + u]; }
+                ok[u] = frame[u] != nullptr && lh[u] != nullptr;
+                any = any || ok[u];
+            }
+            if (!any) continue;
+            // per lane: did this candidate find the pixel, and where on its template
+            if (cells[(long long)k * n + p] < 0) continue;
+            const float4 src = tables[(long long)k * n + p];
+            const TsSampler smp(src.x, src.y, sx, sy, H, W);     // ts_query_kernel's sampler at the candidate's template point
+            uint2 q[TF_FW][4];
+            float l[TF_FW][8];
+#pragma unroll
+            for (int u = 0; u < TF_FW; ++u) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) q[u][j] = make_uint2(0u, 0u);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) l[u][j] = 0.f;
+                if (ok[u]) {
+                    smp.load(frame[u], q[u]);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) l[u][j] = lh[u][j];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < TF_FW; ++u) {
+                if (!ok[u]) continue;
+                const float4 m = smp.mix(Dec4(l[u]), q[u]);
+                // chained exactly as ts_flow_from_kernel chains (the NaN-keeping maximum and the float64 root: see there)
+                const float qx = src.x + m.x, qy = src.y + m.y, od = m.z, sd = m.w;
+                const float ss = src.w * src.w + sd * sd;
+                const float fx = qx - x, fy = qy - y;
+                const float oc = src.z != src.z ? src.z : (od != od ? od : fmaxf(src.z, od));
+                const float sg = (float)sqrt((double)ss);
+                const unsigned field = sg != sg ? 0x7fffffffu : (sg > 0.f ? __float_as_uint(sg) : 0u);
+                const unsigned long long key = ((unsigned long long)(oc <= thr ? 0u : 1u) << 39) | ((unsigned long long)field << 8) | rank;
+                if (key < best[u]) { best[u] = key; bx[u] = fx; by[u] = fy; bo[u] = oc; bs[u] = sg; }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < TF_FW; ++u) {
+            if (t + u >= t1) continue;
+            const long long c = t + u;
+            flow[2 * c * n + p] = bx[u];
+            flow[(2 * c + 1) * n + p] = by[u];
+            occl[c * n + p] = bo[u];
+            sigma[c * n + p] = bs[u];
+            entry[c * n + p] = best[u] == TL_NONE ? -1 : (int)(best[u] & 0xffull);
+        }
+    }
+}
+
 static int ts_blocks(long long n) {
     const long long b = (n + (long long)TS_T * TS_PX - 1) / ((long long)TS_T * TS_PX);
     return (int)(b < 1 ? 1 : (b > TS_B_MAX ? TS_B_MAX : b));
@@ -923,4 +1027,41 @@ extern "C" int mftx_trackstore_flow_from(const float *table, const int *entry, c
                        reinterpret_cast<const float4 *>(table), entry, row_of, reinterpret_cast<const uint2 *const *>(frames), lohis, n_ranks,
                        R, T, cols, H, W, sx, sy, flow, occl, sigma);
     return check_launch("trackstore_flow_from");
+}
+
+extern "C" int mftx_trackstore_flow_from_best(const float *tables, const int *cells, const int *rank_of, const int *row_of,
+                                              const uint16_t *const *frames, const float *const *lohis, int E, int R, int T, int H, int W,
+                                              float occlusion_threshold, int columns_per_block, float *flow, float *occl, float *sigma,
+                                              int *entry, void *stream) {
+    if (T < 0 || E < 0) return fail(MFTX_E_ARG, "trackstore_flow_from_best: need T >= 0, E >= 0");
+    if (E > TFB_ENTRIES) return fail(MFTX_E_ARG, "trackstore_flow_from_best: %d candidates: more than %d", E, TFB_ENTRIES);
+    if (H < 2 || W < 2) return fail(MFTX_E_ARG, "trackstore_flow_from_best: H and W must be >= 2");
+    if (columns_per_block < 0) return fail(MFTX_E_ARG, "trackstore_flow_from_best: columns_per_block must be >= 0 (0: the default)");
+    if ((long long)H * W > 0x7fffffffLL) return fail(MFTX_E_ARG, "trackstore_flow_from_best: more than 2^31 - 1 pixels");
+    if (T == 0) return 0;
+    if (E > 0 && R < 1) return fail(MFTX_E_ARG, "trackstore_flow_from_best: need R >= 1");
+    const struct { const void *p; const char *name; bool always; } ptrs[] = {
+        {tables, "tables", false}, {cells, "cells", false}, {rank_of, "rank_of", false}, {row_of, "row_of", false}, {frames, "frames", false},
+        {lohis, "lohis", false}, {flow, "flow", true}, {occl, "occl", true}, {sigma, "sigma", true}, {entry, "entry", true}};
+    for (const auto &a : ptrs)           // (without candidates nothing but the results is touched)
+        if (!a.p && (a.always || E > 0)) return fail(MFTX_E_ARG, "trackstore_flow_from_best: null pointer: %s", a.name);
+    const int cols = columns_per_block ? columns_per_block : TFB_COLS;
+    const long long blocks = ((long long)H * W + 255) / 256, col_blocks = ((long long)T + cols - 1) / cols;
+    if (col_blocks > 65535)
+        return fail(MFTX_E_ARG, "trackstore_flow_from_best: T = %d in blocks of %d columns: more than 65535 column blocks", T, cols);
+    if (!aligned16(tables)) return fail(MFTX_E_ALIGN, "trackstore_flow_from_best: tables must be 16-byte aligned");
+    if (!aligned_to(frames, 8) || !aligned_to(lohis, 8))
+        return fail(MFTX_E_ALIGN, "trackstore_flow_from_best: the pointer tables frames and lohis must be 8-byte aligned");
+    for (const auto &a : ptrs)
+        if (!aligned_to(a.p, 4)) return fail(MFTX_E_ALIGN, "trackstore_flow_from_best: %s must be 4-byte aligned", a.name);
+    const float sx = (float)(2.0 / (double)(W - 1)), sy = (float)(2.0 / (double)(H - 1));      // as mftx_trackstore_query has them
+    hipStream_t s = (hipStream_t)stream;
+    // per pixel, candidate and group of TF_FW columns: a row and a cell; per pixel, column and candidate (at most): 4 taps of 8 B; per
+    // pixel and column: 20 B of results
+    ProfScope prof(PC_CHAIN, s, 20.0 * (double)H * W * (double)E * (double)((T + TF_FW - 1) / TF_FW) +
+                                    32.0 * (double)H * W * (double)T * (double)E + 20.0 * (double)H * W * (double)T);
+    hipLaunchKernelGGL(ts_flow_best_kernel, dim3((unsigned)blocks, (unsigned)col_blocks), dim3(256), 0, s,
+                       reinterpret_cast<const float4 *>(tables), cells, rank_of, row_of, reinterpret_cast<const uint2 *const *>(frames), lohis, E,
+                       R, T, cols, H, W, sx, sy, occlusion_threshold, flow, occl, sigma, entry);
+    return check_launch("trackstore_flow_from_best");
 }

@@ -13,7 +13,9 @@ frame -- and a template in the middle of a video has its forward and backward ha
     coords, occl, found, template = atlas.tracks_from(points, 57)     # numpy (N, T, 2), (N, T), (N,), (N,): ONE download
     flow, occl, sigma, found, template = atlas.results_from(57)       # device [T, 2, H, W], [T, 1, H, W] x 2, [H, W] x 2: EVERY pixel
     result, found, template = atlas.result_from(57, 80)               # ... one column as a FlowOUTrackingResult
-    atlas.covered(template_frame)                                     # list of bool: the frames some entry of that template holds
+    flow, occl, sigma, entry, template = atlas.best_results_from(57)  # ... the template chosen per pixel AND column: [T, H, W] x 2
+    result, found, template = atlas.best_result_from(57, 12)          # ... one column of that
+    atlas.covered(template_frame)                                    # list of bool: the frames some entry of that template holds
 
 The definition (and the ``device="cpu"`` path; there is no new arithmetic): for a query on frame ``f`` every entry whose store holds
 ``f`` answers with its own ``store.locate(point, f, thr)``; among the entries that found it the smallest
@@ -29,6 +31,12 @@ entries of a video frame onto one key plane.  The two are different code and agr
 ``results_from`` is the dense counterpart of ``tracks_from``: ``inverse``, then every pixel's template point followed by ``query`` on
 its own winner's template and chained behind the inverse as ``DenseTrackStore.results_from`` chains.  On the device that second
 step is ONE ``mftx_trackstore_flow_from`` call, which goes from the inverse's plane straight to planar results.
+
+``results_from`` picks ONE entry per source pixel and follows it through every column, so a column that entry's template does not
+cover is fill even where another template sees the pixel and holds the column -- from a template's own frame back to an earlier
+frame that is every pixel.  ``best_results_from`` makes every entry that holds the source frame a candidate and lets the smallest
+(occluded, chained sigma, rank) win each (pixel, column): per-entry inverses, then ONE ``mftx_trackstore_flow_from_best`` launch
+(mft_amd/atlas_ops.py).
 """
 from __future__ import annotations
 
@@ -367,3 +375,118 @@ class TrackAtlas:
         self._holders(dst)
         flow, occl, sigma, found, template = self.results_from(src, [dst], occlusion_threshold)
         return FlowOUTrackingResult(flow[0], occl[0], sigma[0], validate=False), found, template
+
+    # ------------------------------------------------------------------ ... the template chosen per pixel AND destination frame
+    def _entry_inverses(self, src, ranks, thr):
+        """Every candidate's OWN dense inverse of frame ``src`` -> (tables [E, H, W, 4], cells [E, H, W]): ``store.inverse(src, thr)`` of
+        the entries ``ranks``, bit for bit.  On the device ONE ``ops.trackstore_invert_atlas`` call with one entry per plane."""
+        E, H, W = len(ranks), self.H, self.W
+        tables = torch.empty((E, H, W, 4), dtype=torch.float32, device=self.device)
+        cells = torch.empty((E, H, W), dtype=torch.int32, device=self.device)
+        if self.native:
+            from . import ops
+            ops.trackstore_invert_atlas([self._frame_views(r, src) for r in ranks], np.arange(E + 1), ranks, tables, cells,
+                                        torch.empty_like(cells), thr)
+        else:
+            for k, r in enumerate(ranks):
+                self.entries[r][1].inverse(src, thr, out=(tables[k], cells[k]))
+        return tables, cells
+
+    def _compose_best(self, tables, cells, ranks, cols, thr):
+        """The definition of ``best_results_from`` in torch, on the atlas's device: tables [E, H, W, 4] and cells [E, H, W] of
+        ``_entry_inverses`` for the candidates ``ranks`` (ascending).  Candidate after candidate: its located template points
+        followed by ``query`` on its template, chained behind ITS inverse by ``chain_behind_inverse``, keyed, and kept where the key
+        is smaller than the best so far -> (flow [T, 2, H, W], occlusion [T, 1, H, W], sigma [T, 1, H, W], entry [T, H, W] int32)."""
+        H, W, T = self.H, self.W, len(cols)
+        N = H * W
+        dev = self.device
+        nan, one, inf, zero = (torch.full((), v, dtype=torch.float32, device=dev) for v in (float("nan"), 1.0, float("inf"), 0.0))
+        flow, occl, sigma = nan.expand(T, 2, N).clone(), one.expand(T, N).clone(), inf.expand(T, N).clone()
+        best = torch.full((T, N), _NOT_FOUND, dtype=torch.int64, device=dev)
+        none = torch.full((), _NOT_FOUND, dtype=torch.int64, device=dev)
+        limit = torch.tensor(thr, dtype=torch.float32, device=dev)
+        grid = self.entries[0][1]._pixel_grid()
+        for k, r in enumerate(ranks):
+            s = self.entries[r][0]
+            cov = np.asarray(self.covered(s, cols), dtype=bool)
+            if not (T and cov.any()):
+                continue
+            tb, found = tables[k].reshape(N, 4), cells[k].reshape(N) >= 0
+            ok = found[:, None] & self._upload(cov)[None, :]
+            q = self.query(s, torch.where(found[:, None], tb[:, 0:2], zero), cols)
+            f, o, sg = chain_behind_inverse(tb, q, grid, ok)                                    # [T, 2, N], [T, N], [T, N]
+            field = torch.where(sg > 0, sg, zero).contiguous().view(torch.int32).to(torch.int64)
+            field = torch.where(torch.isnan(sg), torch.full((), 0x7fffffff, dtype=torch.int64, device=dev), field)
+            key = ((~(o <= limit)).to(torch.int64) << 39) | (field << 8) | int(r)
+            key = torch.where(ok.t(), key, none)
+            better = key < best
+            best = torch.where(better, key, best)
+            flow, occl, sigma = torch.where(better[:, None, :], f, flow), torch.where(better, o, occl), torch.where(better, sg, sigma)
+        entry = torch.where(best != none, (best & 0xff).to(torch.int32), torch.full((), -1, dtype=torch.int32, device=dev))
+        return flow.reshape(T, 2, H, W), occl.reshape(T, 1, H, W), sigma.reshape(T, 1, H, W), entry.reshape(T, H, W)
+
+    def _best_tables(self, ranks, cols):
+        """The host tables of ``atlas_ops.trackstore_flow_from_best`` -> (rank_of [E], row_of [E], frame_ptrs [R, T], lohi_ptrs [R, T])."""
+        row_of, frame_ptrs, lohi_ptrs = self._flow_tables(cols)
+        return list(ranks), [row_of[r] for r in ranks], frame_ptrs, lohi_ptrs
+
+    def best_results_from(self, src, frames=None, occlusion_threshold=0.5, out=None):
+        """``results_from`` with the template chosen per pixel AND destination frame -> (flow [T, 2, H, W], occlusion [T, 1, H, W],
+        sigma [T, 1, H, W], entry [T, H, W] int32, template [T, H, W] int32) on the atlas's device.  ``results_from`` follows each
+        pixel on the one entry that sees it best on ``src`` and fills the columns that entry's template does not cover, although
+        another template may see the pixel on ``src`` AND hold the destination -- from a template's own frame back to an earlier
+        frame that is every pixel.  Here the candidates are ALL entries that hold ``src``, in ascending rank; candidate k takes
+        pixel p back by its own ``store.inverse(src)`` (it finds p iff its cell is >= 0), follows that template point by ``query``
+        on its template and chains as ``results_from`` chains.  It has an answer for (p, column t) iff it finds p and its template
+        covers t, and among those the smallest key wins,
+
+            key = (occluded << 39) | (sigma_field << 8) | rank,   occluded = not (o <= occlusion_threshold),
+            sigma_field = 0x7fffffff for a NaN sigma, the float32 bits of s for s > 0, 0 otherwise,
+
+        with o and s the CHAINED occlusion and sigma: visible before occluded, then the lowest chained sigma, then the lowest rank.
+        This is deliberately NOT ``locate``'s key in two respects: a NaN occlusion counts as occluded, and a NaN sigma sorts behind
+        every number, +inf included -- in a choice among alternatives a NaN must never beat a number.  ``entry`` is the winner's
+        rank and ``template`` its template frame; where no candidate has an answer: NaN flow, occlusion 1, sigma +inf, -1, -1.
+        The winner of ``inverse`` is one of the candidates, so a pixel-column ``results_from`` answers is answered here, by a key
+        that is no larger.  ``out``: a (flow, occlusion, sigma) triple as for ``results_from``; ``entry`` and ``template`` are
+        allocated by the call.  ``KeyError`` for a ``src`` that no entry holds, ``ValueError`` for an ``out`` that does not fit, both
+        before any work.  On the device: the E candidates' inverses in ONE ``mftx_trackstore_invert_atlas`` call (one entry per
+        plane; 32 bytes of planes and workspace per pixel and candidate -- 84 MB for 10 candidates at 512 x 512, 2.1 GB for 32 at
+        1080 x 1920 -- freed when the call returns), one table upload and ONE ``mftx_trackstore_flow_from_best`` launch; no host
+        synchronisation."""
+        ranks = self._holders(src)                                              # KeyError before any work
+        cols = list(self.frames) if frames is None else [int(f) for f in frames]
+        H, W, T = self.H, self.W, len(cols)
+        shapes = ((T, 2, H, W), (T, 1, H, W), (T, 1, H, W))
+        if out is not None:
+            out = tuple(out)
+            if len(out) != 3 or any(not isinstance(o, torch.Tensor) or tuple(o.shape) != s or o.dtype != torch.float32 or
+                                    not _same_device(o.device, self.device) or not o.is_contiguous() for o, s in zip(out, shapes)):
+                raise ValueError(f"TrackAtlas.best_results_from: out must be contiguous float32 tensors {[list(s) for s in shapes]} on {self.device}")
+        thr = float(occlusion_threshold)
+        if T:
+            tables, cells = self._entry_inverses(src, ranks, thr)           # (before the results are allocated: its workspace is the peak)
+        if out is None:
+            out = tuple(torch.empty(s, dtype=torch.float32, device=self.device) for s in shapes)
+        entry = torch.full((T, H, W), -1, dtype=torch.int32, device=self.device)
+        if T:
+            if self.native:
+                from . import atlas_ops
+                atlas_ops.trackstore_flow_from_best(tables, cells, *self._best_tables(ranks, cols), *out, entry, thr)
+            else:
+                *planes, entry = self._compose_best(tables, cells, ranks, cols, thr)
+                for o, v in zip(out, planes):
+                    o.copy_(v)
+        tmpl_of = self._upload(np.asarray([f for f, _ in self.entries], dtype=np.int32))
+        template = torch.where(entry >= 0, tmpl_of[entry.clamp(min=0).to(torch.int64)], torch.full((), -1, dtype=torch.int32, device=self.device))
+        return out[0], out[1], out[2], entry, template
+
+    def best_result_from(self, src, dst, occlusion_threshold=0.5):
+        """-> (``FlowOUTrackingResult`` of the flow from video frame ``src`` to video frame ``dst``, found [H, W] bool, template
+        [H, W] int32): one column of ``best_results_from``; found = some candidate answers the pixel for ``dst`` (mask the others:
+        their flow is NaN).  ``KeyError`` for a ``src`` or a ``dst`` that no entry holds."""
+        from .results import FlowOUTrackingResult
+        self._holders(src)
+        self._holders(dst)
+        flow, occl, sigma, entry, template = self.best_results_from(src, [dst], occlusion_threshold)
+        return FlowOUTrackingResult(flow[0], occl[0], sigma[0], validate=False), entry[0] >= 0, template[0]

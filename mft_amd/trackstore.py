@@ -448,10 +448,23 @@ class DenseTrackStore:
         Pixel p = (x, y) of ``src`` is taken back to its template point by ``inverse(src)`` -- (Px, Py, o_src, s_src) -- and that
         point forward by ``query`` -- (qx, qy, o_dst, s_dst) on frame t: flow = (qx - x, qy - y), occlusion = max(o_src, o_dst),
         sigma = sqrt(s_src^2 + s_dst^2), the rule by which results are chained (MFT/MFT.py:233-239) with the inverse as the left
-        result.  A pixel nothing maps to has found False, NaN flow, occlusion 1 and sigma +inf.  No host synchronisation."""
+        result.  A pixel nothing maps to has found False, NaN flow, occlusion 1 and sigma +inf.  On the device the read-out and the
+        chaining are ONE ``mftx_trackstore_flow_from`` call behind ``inverse`` (a one-row table, every found pixel entry 0), bit for
+        bit the composition below.  No host synchronisation."""
         H, W = self.H, self.W
         slots = self._slots(frames)                             # KeyError before any work
         table, cell = self.inverse(src, occlusion_threshold)
+        if self.native:
+            from . import ops
+            T = len(slots)
+            flow = torch.empty((T, 2, H, W), dtype=torch.float32, device=self.device)
+            occl, sigma = (torch.empty((T, 1, H, W), dtype=torch.float32, device=self.device) for _ in range(2))
+            found = cell >= 0
+            if T:
+                entry = torch.where(found, 0, -1).to(torch.int32)
+                frame_ptrs, lohi_ptrs = ops.trackstore_slot_addresses(self._chunks, self._lohi, slots)
+                ops.trackstore_flow_from(table, entry, [0], frame_ptrs[None], lohi_ptrs[None], flow, occl, sigma)
+            return flow, occl, sigma, found
         table, found = table.view(H * W, 4), cell.view(H * W) >= 0
         zero = torch.zeros((), dtype=torch.float32, device=self.device)
         template = torch.where(found[:, None], table[:, 0:2], zero)
