@@ -14,11 +14,15 @@
 // The reference does 3 grid_samples + ~25 launches per candidate and a
 // stack/max/gather pass; here one thread owns a pixel, walks the K candidates,
 // and keeps the running best in registers: (32 K + 16) B/pixel of traffic.
-// `chain_px` is shared by all three kernels so that chain -> all-gather ->
-// select (multi-GPU) is bitwise identical to the fused single-GPU kernel.
+// Every kernel here gives the same bits for the same operands -- chain -> all-gather -> select (multi-GPU) is bitwise the
+// fused single-GPU kernel, planar and packed and multi-template variants agree -- because each piece of arithmetic is
+// written once: B (coordinate round trip, weights, order of the sum, both tap policies) in grid_sample.h, which
+// trackstore.hip shares; the chaining rule in `chained()`; the selection in `consider()`; the two walks over the candidates
+// in `MFTX_BEST_BATCHED` and `best_sequential()`.
 // Compiled with -ffp-contract=off: no FMA contraction, products and sums round
 // exactly as written.
 #include "common.h"
+#include "grid_sample.h"
 #include "profile.h"
 #include <initializer_list>
 
@@ -27,42 +31,40 @@ namespace mftx {
 struct Planes { const float *flow, *occl, *sigma; };
 struct Chained { float fx, fy, occ, sig; };
 
-__device__ __forceinline__ float tap(const float *pl, int H, int W, int yy, int xx) {
-    return (yy >= 0 && yy < H && xx >= 0 && xx < W) ? pl[(long long)yy * W + xx] : 0.f;
-}
-
 // NaN handling follows torch: a NaN sampled occlusion propagates through
 // maximum(); fmaxf would drop it, so patch it up explicitly.
 __device__ __forceinline__ float max_nanprop(float a, float b) {
     return (a != a || b != b) ? NAN : fmaxf(a, b);
 }
 
+// Pixel g = (x, y) with its left flow: p = g + flowL and the sampler there.
+struct ChainPrep { float px, py, gx, gy; GridSample s; };
+
+__device__ __forceinline__ ChainPrep chain_prep(float lfx, float lfy, int H, int W, int x, int y, float sx, float sy) {
+    const float gx = (float)x, gy = (float)y;
+    const float px = gx + lfx, py = gy + lfy;
+    return ChainPrep{px, py, gx, gy, grid_sample_at(px, py, sx, sy, H, W)};
+}
+
+// The chaining rule: the left operand's occlusion and sigma with r = B(flow x, flow y, occlusion, sigma of the right operand).
+__device__ __forceinline__ Chained chained(const ChainPrep &c, float locc, float lsig, const float4 &r) {
+    Chained o;
+    o.fx = (c.px + r.x) - c.gx;
+    o.fy = (c.py + r.y) - c.gy;
+    o.occ = max_nanprop(locc, r.z);
+    o.sig = sqrtf(lsig * lsig + r.w * r.w);
+    return o;
+}
+
+// planar right operand: bounds-tested taps
 __device__ __forceinline__ Chained chain_px(const Planes &L, const Planes &R, int H, int W, int x, int y,
                                            float sx, float sy) {
     const long long pix = (long long)y * W + x;
     const long long plane = (long long)H * W;
-    const float gx = (float)x, gy = (float)y;
-    const float px = gx + L.flow[pix];
-    const float py = gy + L.flow[plane + pix];
-    // normalise: p * float32(2/(W-1)) - 1 ; un-normalise: ((g + 1) / 2) * (W - 1)
-    const float ix = ((px * sx - 1.f) + 1.f) / 2.f * (float)(W - 1);
-    const float iy = ((py * sy - 1.f) + 1.f) / 2.f * (float)(H - 1);
-    const float flx = floorf(ix), fly = floorf(iy);
-    const float wx = ix - flx, wy = iy - fly;
-    const int x0 = (int)fminf(fmaxf(flx, -1.0e6f), 1.0e6f);
-    const int y0 = (int)fminf(fmaxf(fly, -1.0e6f), 1.0e6f);
-    const float w00 = (1.f - wx) * (1.f - wy), w01 = wx * (1.f - wy), w10 = (1.f - wx) * wy, w11 = wx * wy;
-    auto samp = [&](const float *pl) {
-        return tap(pl, H, W, y0, x0) * w00 + tap(pl, H, W, y0, x0 + 1) * w01 +
-               tap(pl, H, W, y0 + 1, x0) * w10 + tap(pl, H, W, y0 + 1, x0 + 1) * w11;
-    };
-    Chained c;
-    c.fx = (px + samp(R.flow)) - gx;
-    c.fy = (py + samp(R.flow + plane)) - gy;
-    c.occ = max_nanprop(L.occl[pix], samp(R.occl));
-    const float sl = L.sigma[pix], sr = samp(R.sigma);
-    c.sig = sqrtf(sl * sl + sr * sr);
-    return c;
+    const ChainPrep c = chain_prep(L.flow[pix], L.flow[plane + pix], H, W, x, y, sx, sy);
+    return chained(c, L.occl[pix], L.sigma[pix],
+                   make_float4(grid_sample(c.s, R.flow, H, W), grid_sample(c.s, R.flow + plane, H, W),
+                               grid_sample(c.s, R.occl, H, W), grid_sample(c.s, R.sigma, H, W)));
 }
 
 __global__ __launch_bounds__(256) void chain_kernel(Planes L, Planes R, int H, int W, float sx, float sy,
@@ -83,20 +85,8 @@ __global__ __launch_bounds__(256) void warp_backward_kernel(const float *__restr
     const int y = blockIdx.y;
     if (x >= W) return;
     const long long pix = (long long)y * W + x, plane = (long long)H * W;
-    const float px = (float)x + flow[pix];
-    const float py = (float)y + flow[plane + pix];
-    const float ix = ((px * sx - 1.f) + 1.f) / 2.f * (float)(W - 1);
-    const float iy = ((py * sy - 1.f) + 1.f) / 2.f * (float)(H - 1);
-    const float flx = floorf(ix), fly = floorf(iy);
-    const float wx = ix - flx, wy = iy - fly;
-    const int x0 = (int)fminf(fmaxf(flx, -1.0e6f), 1.0e6f);
-    const int y0 = (int)fminf(fmaxf(fly, -1.0e6f), 1.0e6f);
-    const float w00 = (1.f - wx) * (1.f - wy), w01 = wx * (1.f - wy), w10 = (1.f - wx) * wy, w11 = wx * wy;
-    for (int c = 0; c < C; ++c) {
-        const float *pl = img + c * plane;
-        out[c * plane + pix] = tap(pl, H, W, y0, x0) * w00 + tap(pl, H, W, y0, x0 + 1) * w01 +
-                               tap(pl, H, W, y0 + 1, x0) * w10 + tap(pl, H, W, y0 + 1, x0 + 1) * w11;
-    }
+    const GridSample s = grid_sample_at((float)x + flow[pix], (float)y + flow[plane + pix], sx, sy, H, W);
+    for (int c = 0; c < C; ++c) out[c * plane + pix] = grid_sample(s, img + c * plane, H, W);
 }
 
 struct CandSet {
@@ -105,7 +95,7 @@ struct CandSet {
     Planes R[MFTX_MAX_CANDIDATES];
 };
 
-struct Best { float score; Chained c; int k; };
+struct Best { float score = 0.f; Chained c = {0.f, 0.f, 0.f, 0.f}; int k = 0; };      // (consider() takes candidate 0 whatever this holds)
 
 __device__ __forceinline__ void consider(Best &b, const Chained &c, int k, float thr) {
     // torch: scores = -sigma; scores[occl > thr] = -inf; max(dim=0) keeps the
@@ -138,7 +128,6 @@ __global__ __launch_bounds__(256) void chain_select_kernel(CandSet cs, float thr
     const int y = blockIdx.y;
     if (x >= W) return;
     Best b;
-    b.score = 0.f; b.k = 0; b.c = Chained{0.f, 0.f, 0.f, 0.f};
     for (int k = 0; k < cs.K; ++k) consider(b, chain_px(cs.L[k], cs.R[k], H, W, x, y, sx, sy), k, thr);
     write_selected(b, H, W, x, y, flowO, occlO, sigmaO, chosen);
 }
@@ -155,7 +144,6 @@ __global__ __launch_bounds__(256) void select_kernel(SelSet ss, float thr, int H
     if (x >= W) return;
     const long long pix = (long long)y * W + x, plane = (long long)H * W;
     Best b;
-    b.score = 0.f; b.k = 0; b.c = Chained{0.f, 0.f, 0.f, 0.f};
     for (int k = 0; k < ss.K; ++k) {
         Chained c;
         c.fx = ss.C[k].flow[pix]; c.fy = ss.C[k].flow[plane + pix];
@@ -166,8 +154,8 @@ __global__ __launch_bounds__(256) void select_kernel(SelSet ss, float thr, int H
 }
 
 // ---- PACKED right operands ([H][W][4] = fx, fy, occl, sigma per pixel, written by the upsampler): each bilinear
-// tap is ONE 16-byte gather instead of four 4-byte ones.  Same arithmetic, operation by operation, as chain_px
-// (bitwise equal results).
+// tap is ONE 16-byte gather instead of four 4-byte ones, blended by the same Bilinear::blend and chained by the same
+// chained() as the planar operands: bitwise equal results.
 struct PackedSet {
     int K;
     Planes L[MFTX_MAX_CANDIDATES];
@@ -195,47 +183,72 @@ __device__ __forceinline__ void write_selected4(const Best (&b)[4], int H, int W
 
 // One pixel per thread, right operands PACKED: 4 coalesced 4-byte loads of the left planes + 4 sixteen-byte gathers
 // per candidate instead of 4 + 16 four-byte gathers (the planar kernel is bound by the texture-address rate of
-// its gathers).  The chain of a candidate is two dependent memory round trips (left planes -> tap addresses -> taps);
-// walked candidate by candidate that is 2 K round trips per thread and the kernel is latency-bound (24 us for 63 MB at
-// K = 7).  With K known at compile time (KT = 1..8) ALL left planes are loaded first, then the taps in batches of
-// four candidates: 1 + ceil(K / 4) round trips.  Taps outside the image are read at a clamped address and replaced by
-// zeros afterwards (no branches).  Same arithmetic, operation by operation, as chain_px: bitwise equal results.
-struct ChainPrep { float px, py, gx, gy, w00, w01, w10, w11; int x0, y0; };
-
-__device__ __forceinline__ ChainPrep chain_prep(float lfx, float lfy, int H, int W, int x, int y, float sx, float sy) {
-    ChainPrep c;
-    c.gx = (float)x; c.gy = (float)y;
-    c.px = c.gx + lfx;
-    c.py = c.gy + lfy;
-    const float ix = ((c.px * sx - 1.f) + 1.f) / 2.f * (float)(W - 1);
-    const float iy = ((c.py * sy - 1.f) + 1.f) / 2.f * (float)(H - 1);
-    const float flx = floorf(ix), fly = floorf(iy);
-    const float wx = ix - flx, wy = iy - fly;
-    c.x0 = (int)fminf(fmaxf(flx, -1.0e6f), 1.0e6f);
-    c.y0 = (int)fminf(fmaxf(fly, -1.0e6f), 1.0e6f);
-    c.w00 = (1.f - wx) * (1.f - wy); c.w01 = wx * (1.f - wy); c.w10 = (1.f - wx) * wy; c.w11 = wx * wy;
-    return c;
-}
-
+// its gathers).  Taps outside the image are read at a clamped address and replaced by zeros afterwards (no branches).
 __device__ __forceinline__ float4 packed_tap(const float4 *R, int H, int W, int yy, int xx) {
-    const bool ok = (yy >= 0) & (yy < H) & (xx >= 0) & (xx < W);
-    const int cy = min(max(yy, 0), H - 1), cx = min(max(xx, 0), W - 1);
-    const float4 v = R[(long long)cy * W + cx];
-    return ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+    bool in;
+    const float4 v = R[clamped_tap(H, W, yy, xx, in)];
+    return in ? v : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-__device__ __forceinline__ Chained chain_finish(const ChainPrep &c, float locc, float lsig, const float4 &a, const float4 &b,
-                                                const float4 &cc, const float4 &d) {
-    Chained o;
-    o.fx = (c.px + (a.x * c.w00 + b.x * c.w01 + cc.x * c.w10 + d.x * c.w11)) - c.gx;
-    o.fy = (c.py + (a.y * c.w00 + b.y * c.w01 + cc.y * c.w10 + d.y * c.w11)) - c.gy;
-    o.occ = max_nanprop(locc, a.z * c.w00 + b.z * c.w01 + cc.z * c.w10 + d.z * c.w11);
-    const float sr = a.w * c.w00 + b.w * c.w01 + cc.w * c.w10 + d.w * c.w11;
-    o.sig = sqrtf(lsig * lsig + sr * sr);
-    return o;
+__device__ __forceinline__ void packed_taps(const float4 *R, const GridSample &s, int H, int W, float4 (&t)[4]) {
+    t[0] = packed_tap(R, H, W, s.y0, s.x0);
+    t[1] = packed_tap(R, H, W, s.y0, s.x0 + 1);
+    t[2] = packed_tap(R, H, W, s.y0 + 1, s.x0);
+    t[3] = packed_tap(R, H, W, s.y0 + 1, s.x0 + 1);
 }
 
-template <int KT>    // KT = number of candidates (1..8), or 0: any K, candidate by candidate
+__device__ __forceinline__ Chained chained(const ChainPrep &c, float locc, float lsig, const float4 (&t)[4]) {
+    return chained(c, locc, lsig, c.s.w.blend(t[0], t[1], t[2], t[3]));
+}
+
+// The chain of a candidate is two dependent memory round trips (left planes -> tap addresses -> taps); walked candidate by
+// candidate that is 2 K round trips per thread and the kernel is latency-bound (24 us for 63 MB at K = 7).  `Set` is anything
+// with candidate k's left planes in L[k] and its packed right operand in R[k] (PackedSet, MultiTmpl).
+template <class Set>
+__device__ __forceinline__ Best best_sequential(const Set &cs, int K, float thr, int H, int W, int x, int y, float sx, float sy) {
+    const long long pix = (long long)y * W + x, plane = (long long)H * W;
+    Best b;
+    for (int k = 0; k < K; ++k) {
+        const Planes L = cs.L[k];
+        const ChainPrep c = chain_prep(L.flow[pix], L.flow[plane + pix], H, W, x, y, sx, sy);
+        float4 t[4];
+        packed_taps(cs.R[k], c.s, H, W, t);
+        consider(b, chained(c, L.occl[pix], L.sigma[pix], t), k, thr);
+    }
+    return b;
+}
+
+// With K <= KB, a compile-time bound of at most 8, ALL left planes are loaded first, then the taps in batches of four candidates:
+// 1 + ceil(K / 4) round trips.  K is KB itself (every `< K` folds) or a run-time value, uniform per block.  A macro, not a
+// function: as a function the compiler simplifies the body on its own before it inlines it, and both kernels came out different
+// from the body written in place -- chain_select_packed_kernel<7> 2 % slower, and chain_select_multi_kernel<8, 12> with the
+// operands of the blend's sums swapped, which NaN bits show ("One sampler").  That order is the compiler's: an upgrade
+// may change it, and tests/test_gpu_chain_family.py (every variant against select, NaN as int32) shows it.  Expands in a
+// kernel's scope: it reads pix, plane, thr, H, W, x, y, sx, sy there.
+#define MFTX_BEST_BATCHED(b, cs, KB, K)                                                                                          \
+    {                                                                                                                            \
+        float lfx[KB], lfy[KB], loc[KB], lsg[KB];                                                                                \
+        _Pragma("unroll") for (int k = 0; k < KB; ++k) {                                                                         \
+            if (k < K) {                                                                                                         \
+                lfx[k] = cs.L[k].flow[pix]; lfy[k] = cs.L[k].flow[plane + pix];                                                  \
+                loc[k] = cs.L[k].occl[pix]; lsg[k] = cs.L[k].sigma[pix];                                                         \
+            }                                                                                                                    \
+        }                                                                                                                        \
+        _Pragma("unroll") for (int k0 = 0; k0 < KB; k0 += 4) {                                                                   \
+            ChainPrep c[4];                                                                                                      \
+            float4 tp[4][4];                                                                                                     \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                                      \
+                if (k0 + j < K) {                                                                                                \
+                    c[j] = chain_prep(lfx[k0 + j], lfy[k0 + j], H, W, x, y, sx, sy);                                             \
+                    packed_taps(cs.R[k0 + j], c[j].s, H, W, tp[j]);                                                              \
+                }                                                                                                                \
+            }                                                                                                                    \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                                        \
+                if (k0 + j < K) consider(b, chained(c[j], loc[k0 + j], lsg[k0 + j], tp[j]), k0 + j, thr);                        \
+        }                                                                                                                        \
+    }
+
+template <int KT>    // KT = number of candidates (1..8): batched taps; or 0: any K, candidate by candidate
 __global__ __launch_bounds__(256) void chain_select_packed_kernel(PackedSet ps, float thr, int H, int W, float sx,
                                                                   float sy, float *flowO, float *occlO, float *sigmaO,
                                                                   int8_t *chosen) {
@@ -244,44 +257,8 @@ __global__ __launch_bounds__(256) void chain_select_packed_kernel(PackedSet ps, 
     if (x >= W) return;
     const long long pix = (long long)y * W + x, plane = (long long)H * W;
     Best b;
-    b.score = 0.f; b.k = 0; b.c = Chained{0.f, 0.f, 0.f, 0.f};
-    if constexpr (KT == 0) {
-        for (int k = 0; k < ps.K; ++k) {
-            const Planes L = ps.L[k];
-            const ChainPrep c = chain_prep(L.flow[pix], L.flow[plane + pix], H, W, x, y, sx, sy);
-            const float4 *R = ps.R[k];
-            consider(b, chain_finish(c, L.occl[pix], L.sigma[pix], packed_tap(R, H, W, c.y0, c.x0), packed_tap(R, H, W, c.y0, c.x0 + 1),
-                                     packed_tap(R, H, W, c.y0 + 1, c.x0), packed_tap(R, H, W, c.y0 + 1, c.x0 + 1)), k, thr);
-        }
-    } else {
-        float lfx[KT], lfy[KT], loc[KT], lsg[KT];
-#pragma unroll
-        for (int k = 0; k < KT; ++k) {
-            lfx[k] = ps.L[k].flow[pix]; lfy[k] = ps.L[k].flow[plane + pix];
-            loc[k] = ps.L[k].occl[pix]; lsg[k] = ps.L[k].sigma[pix];
-        }
-#pragma unroll
-        for (int k0 = 0; k0 < KT; k0 += 4) {
-            constexpr int B = 4;
-            ChainPrep c[B];
-            float4 t[B][4];
-#pragma unroll
-            for (int j = 0; j < B; ++j) {
-                if (k0 + j < KT) {
-                    c[j] = chain_prep(lfx[k0 + j], lfy[k0 + j], H, W, x, y, sx, sy);
-                    const float4 *R = ps.R[k0 + j];
-                    t[j][0] = packed_tap(R, H, W, c[j].y0, c[j].x0);
-                    t[j][1] = packed_tap(R, H, W, c[j].y0, c[j].x0 + 1);
-                    t[j][2] = packed_tap(R, H, W, c[j].y0 + 1, c[j].x0);
-                    t[j][3] = packed_tap(R, H, W, c[j].y0 + 1, c[j].x0 + 1);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < B; ++j)
-                if (k0 + j < KT)
-                    consider(b, chain_finish(c[j], loc[k0 + j], lsg[k0 + j], t[j][0], t[j][1], t[j][2], t[j][3]), k0 + j, thr);
-        }
-    }
+    if constexpr (KT == 0) b = best_sequential(ps, ps.K, thr, H, W, x, y, sx, sy);
+    else MFTX_BEST_BATCHED(b, ps, KT, KT)
     write_selected(b, H, W, x, y, flowO, occlO, sigmaO, chosen);
 }
 
@@ -292,8 +269,6 @@ __global__ __launch_bounds__(256) void select4_kernel(SelSet ss, float thr, int 
     if (x >= W) return;
     const long long pix = (long long)y * W + x, plane = (long long)H * W;
     Best b[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { b[i].score = 0.f; b[i].k = 0; b[i].c = Chained{0.f, 0.f, 0.f, 0.f}; }
     for (int k = 0; k < ss.K; ++k) {
         const float4 fx = *reinterpret_cast<const float4 *>(ss.C[k].flow + pix);
         const float4 fy = *reinterpret_cast<const float4 *>(ss.C[k].flow + plane + pix);
@@ -308,13 +283,12 @@ __global__ __launch_bounds__(256) void select4_kernel(SelSet ss, float thr, int 
 }
 
 // ---- MANY TEMPLATES of one video in one launch (mft_amd/multi.py): template j = blockIdx.z chains its own K[j] candidates
-// and selects among them.  Per pixel the arithmetic is chain_select_packed_kernel's, operation for operation -- the output of
-// template j is bitwise what mftx_chain_select_packed gives for that template's candidates alone -- and so is the latency
-// structure: all left planes first, then the taps in batches of four candidates.  K is a run-time value below the
-// compile-time bound KMAX, uniform per block (no divergence).  The descriptors travel by value in the kernel arguments (they
-// are read with scalar loads, indexed by blockIdx.z); a launch's argument block is limited to 4 KB, hence TN templates per
-// launch.  The right operands the templates share (the finite-delta pairs of a frame) are read once from HBM and then
-// from L2 / Infinity Cache by the other templates' blocks.
+// and selects among them with chain_select_packed_kernel's two walks -- the output of template j is bitwise what
+// mftx_chain_select_packed gives for that template's candidates alone.  K is a run-time value below the compile-time bound
+// KMAX, uniform per block (no divergence).  The descriptors travel by value in the kernel arguments (they are read with
+// scalar loads, indexed by blockIdx.z); a launch's argument block is limited to 4 KB, hence TN templates per launch.  The
+// right operands the templates share (the finite-delta pairs of a frame) are read once from HBM and then from L2 /
+// Infinity Cache by the other templates' blocks.
 template <int KMAX>
 struct MultiTmpl {
     int K;
@@ -330,7 +304,7 @@ struct MultiSet { MultiTmpl<KMAX> t[TN]; };
 static_assert(sizeof(MultiSet<8, MULTI_TN8>) + 32 <= 4096 && sizeof(MultiSet<MFTX_MAX_CANDIDATES, MULTI_TN16>) + 32 <= 4096,
               "kernel arguments of chain_select_multi_kernel exceed 4 KB");
 
-template <int KMAX, int TN>     // KMAX = 8: batched taps; KMAX = 16: any K, candidate by candidate (as chain_select_packed_kernel<0>)
+template <int KMAX, int TN>     // KMAX = 8: batched taps; KMAX = 16: any K, candidate by candidate
 __global__ __launch_bounds__(256) void chain_select_multi_kernel(MultiSet<KMAX, TN> ms, float thr, int H, int W, float sx,
                                                                  float sy) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
@@ -340,52 +314,15 @@ __global__ __launch_bounds__(256) void chain_select_multi_kernel(MultiSet<KMAX, 
     const int K = t.K;
     const long long pix = (long long)y * W + x, plane = (long long)H * W;
     Best b;
-    b.score = 0.f; b.k = 0; b.c = Chained{0.f, 0.f, 0.f, 0.f};
-    if constexpr (KMAX > 8) {
-        for (int k = 0; k < K; ++k) {
-            const Planes L = t.L[k];
-            const ChainPrep c = chain_prep(L.flow[pix], L.flow[plane + pix], H, W, x, y, sx, sy);
-            const float4 *R = t.R[k];
-            consider(b, chain_finish(c, L.occl[pix], L.sigma[pix], packed_tap(R, H, W, c.y0, c.x0), packed_tap(R, H, W, c.y0, c.x0 + 1),
-                                     packed_tap(R, H, W, c.y0 + 1, c.x0), packed_tap(R, H, W, c.y0 + 1, c.x0 + 1)), k, thr);
-        }
-    } else {
-        float lfx[KMAX], lfy[KMAX], loc[KMAX], lsg[KMAX];
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) {
-            if (k < K) {
-                lfx[k] = t.L[k].flow[pix]; lfy[k] = t.L[k].flow[plane + pix];
-                loc[k] = t.L[k].occl[pix]; lsg[k] = t.L[k].sigma[pix];
-            }
-        }
-#pragma unroll
-        for (int k0 = 0; k0 < KMAX; k0 += 4) {
-            constexpr int B = 4;
-            ChainPrep c[B];
-            float4 tp[B][4];
-#pragma unroll
-            for (int j = 0; j < B; ++j) {
-                if (k0 + j < K) {
-                    c[j] = chain_prep(lfx[k0 + j], lfy[k0 + j], H, W, x, y, sx, sy);
-                    const float4 *R = t.R[k0 + j];
-                    tp[j][0] = packed_tap(R, H, W, c[j].y0, c[j].x0);
-                    tp[j][1] = packed_tap(R, H, W, c[j].y0, c[j].x0 + 1);
-                    tp[j][2] = packed_tap(R, H, W, c[j].y0 + 1, c[j].x0);
-                    tp[j][3] = packed_tap(R, H, W, c[j].y0 + 1, c[j].x0 + 1);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < B; ++j)
-                if (k0 + j < K)
-                    consider(b, chain_finish(c[j], loc[k0 + j], lsg[k0 + j], tp[j][0], tp[j][1], tp[j][2], tp[j][3]), k0 + j, thr);
-        }
-    }
+    if constexpr (KMAX > 8) b = best_sequential(t, K, thr, H, W, x, y, sx, sy);
+    else MFTX_BEST_BATCHED(b, t, KMAX, K)
     write_selected(b, H, W, x, y, t.flowO, t.occlO, t.sigmaO, t.chosen);
 }
+#undef MFTX_BEST_BATCHED
 
 // ---- point read-out of many templates' results in one launch (MFT/point_tracking.py:6-27: warp_forward_points + sample).
 // Point i belongs to template tmpl[i] and sits at (xy[2 i], xy[2 i + 1]) on that template's frame: its flow / occlusion /
-// sigma planes are sampled there with chain_px's sampler (bilinear, zeros outside, align_corners=True, after the
+// sigma planes are sampled there with grid_sample.h's sampler (bilinear, zeros outside, align_corners=True, after the
 // normalise / un-normalise round trip) and (x + fx, y + fy, occlusion, sigma) goes, as ONE 16-byte store, to row i, column
 // `column` of the caller's table.  One thread per point; a launch carries the planes of up to SAMPLE_TN templates in its
 // arguments and leaves the points of other templates alone.
@@ -403,18 +340,9 @@ __global__ __launch_bounds__(256) void sample_points_kernel(SampleSet ss, int t0
     const Planes P = ss.t[j];
     const long long plane = (long long)H * W;
     const float px = xy[2 * (long long)i], py = xy[2 * (long long)i + 1];
-    const float ix = ((px * sx - 1.f) + 1.f) / 2.f * (float)(W - 1);
-    const float iy = ((py * sy - 1.f) + 1.f) / 2.f * (float)(H - 1);
-    const float flx = floorf(ix), fly = floorf(iy);
-    const float wx = ix - flx, wy = iy - fly;
-    const int x0 = (int)fminf(fmaxf(flx, -1.0e6f), 1.0e6f);
-    const int y0 = (int)fminf(fmaxf(fly, -1.0e6f), 1.0e6f);
-    const float w00 = (1.f - wx) * (1.f - wy), w01 = wx * (1.f - wy), w10 = (1.f - wx) * wy, w11 = wx * wy;
-    auto samp = [&](const float *pl) {
-        return tap(pl, H, W, y0, x0) * w00 + tap(pl, H, W, y0, x0 + 1) * w01 +
-               tap(pl, H, W, y0 + 1, x0) * w10 + tap(pl, H, W, y0 + 1, x0 + 1) * w11;
-    };
-    const float4 o = make_float4(px + samp(P.flow), py + samp(P.flow + plane), samp(P.occl), samp(P.sigma));
+    const GridSample s = grid_sample_at(px, py, sx, sy, H, W);
+    const float4 o = make_float4(px + grid_sample(s, P.flow, H, W), py + grid_sample(s, P.flow + plane, H, W),
+                                 grid_sample(s, P.occl, H, W), grid_sample(s, P.sigma, H, W));
     *reinterpret_cast<float4 *>(table + (long long)i * row_stride + 4 * (long long)column) = o;
 }
 
@@ -429,12 +357,6 @@ static bool vec4_ok(int W, std::initializer_list<const void *> ptrs) {
     return true;
 }
 
-static void scales(int H, int W, float &sx, float &sy) {
-    // np.array([2/(W-1), 2/(H-1)]).astype(np.float32)  (double division, then rounded)
-    sx = (float)(2.0 / (double)(W - 1));
-    sy = (float)(2.0 / (double)(H - 1));
-}
-
 extern "C" int mftx_chain(const float *flowL, const float *occlL, const float *sigmaL, const float *flowR,
                           const float *occlR, const float *sigmaR, int H, int W, float *flowO, float *occlO,
                           float *sigmaO, void *stream) {
@@ -442,7 +364,7 @@ extern "C" int mftx_chain(const float *flowL, const float *occlL, const float *s
         return fail(MFTX_E_ARG, "chain: null pointer");
     if (H < 2 || W < 2) return fail(MFTX_E_ARG, "chain: H and W must be >= 2");
     float sx, sy;
-    scales(H, W, sx, sy);
+    grid_scales(H, W, sx, sy);
     Planes L{flowL, occlL, sigmaL}, R{flowR, occlR, sigmaR};
     ProfScope prof(PC_CHAIN, (hipStream_t)stream, 48.0 * H * W);
     hipLaunchKernelGGL(chain_kernel, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, L, R, H, W, sx, sy,
@@ -455,7 +377,7 @@ extern "C" int mftx_warp_backward(const float *flow, const float *img, int C, in
     if (!flow || !img || !out) return fail(MFTX_E_ARG, "warp_backward: null pointer");
     if (C < 1 || H < 2 || W < 2) return fail(MFTX_E_ARG, "warp_backward: need C >= 1, H, W >= 2");
     float sx, sy;
-    scales(H, W, sx, sy);
+    grid_scales(H, W, sx, sy);
     hipLaunchKernelGGL(warp_backward_kernel, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, flow, img,
                        C, H, W, sx, sy, out);
     return check_launch("warp_backward");
@@ -503,7 +425,7 @@ extern "C" int mftx_chain_select(int K, const float *const *flowL, const float *
         cs.R[k] = Planes{flowR[k], occlR[k], sigmaR[k]};
     }
     float sx, sy;
-    scales(H, W, sx, sy);
+    grid_scales(H, W, sx, sy);
     ProfScope prof(PC_CHAIN, (hipStream_t)stream, (32.0 * K + 16.0) * H * W);
     hipLaunchKernelGGL(chain_select_kernel, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, cs, thr, H,
                        W, sx, sy, flowO, occlO, sigmaO, chosen);
@@ -528,7 +450,7 @@ extern "C" int mftx_chain_select_packed(int K, const float *const *flowL, const 
         ps.R[k] = reinterpret_cast<const float4 *>(packedR[k]);
     }
     float sx, sy;
-    scales(H, W, sx, sy);
+    grid_scales(H, W, sx, sy);
     ProfScope prof(PC_CHAIN, (hipStream_t)stream, (32.0 * K + 16.0) * H * W);
 #define CSP_LAUNCH(KT)                                                                                               \
     hipLaunchKernelGGL(chain_select_packed_kernel<KT>, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, ps, thr, H, \
@@ -591,7 +513,7 @@ extern "C" int mftx_chain_select_multi(int T, const int *K, const float *const *
         maxK = K[j] > maxK ? K[j] : maxK;
     }
     float sx, sy;
-    scales(H, W, sx, sy);
+    grid_scales(H, W, sx, sy);
     // bytes per pixel: every left operand (16) and every output (16) once, every DISTINCT right operand (16) once
     double bytes = 0.0;
     if (prof_enabled()) {
@@ -635,7 +557,7 @@ extern "C" int mftx_sample_points(int T, const float *const *flow, const float *
         return fail(MFTX_E_ARG, "sample_points: row_stride must be a multiple of 4 floats that holds column %d", column);
     if (!aligned16(table)) return fail(MFTX_E_ALIGN, "sample_points: the table must be 16-byte aligned");
     float sx, sy;
-    scales(H, W, sx, sy);
+    grid_scales(H, W, sx, sy);
     // per point: template index + xy (12 B), 4 taps of 4 planes (64 B), one table entry (16 B)
     ProfScope prof(PC_CHAIN, (hipStream_t)stream, (12.0 + 64.0 + 16.0) * N);
     for (int t0 = 0; t0 < T; t0 += SAMPLE_TN) {

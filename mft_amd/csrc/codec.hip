@@ -1,9 +1,6 @@
-// Flow-cache codec on the device: the ".flowouX16" quantisation of
-// MFT/utils/io.py:495-512 (write) and :548-551 (read), per channel:
-//   lb = min(x), ub = max(x)
-//   q  = uint16(round_half_even( (x - lb) / (ub - lb) * 65535 ))     (all zeros if |ub - lb| < 1e-8)
-//   x' = (float(q) / 65535) * (ub - lb) + lb
-// in float32, operation by operation as numpy does it (compiled with -ffp-contract=off).
+// Flow-cache codec on the device: the ".flowouX16" quantisation -- per-channel min/max, uint16, round-half-even;
+// its arithmetic and the workgroup min/max reduction live in quant_u16.h, shared with trackstore.hip (compiled with
+// -ffp-contract=off).
 // Quantising on the device halves the bytes that cross PCIe when a cache entry is
 // spilled to disk; the PNG container around the uint16 planes is host work
 // (mft_amd/flowou_codec.py), with the one inherently serial step -- PNG row
@@ -13,6 +10,7 @@
 // the second pass re-reduces the per-block partials instead of a third launch.
 #include "common.h"
 #include "profile.h"
+#include "quant_u16.h"
 #include <cfloat>
 #include <cstdlib>
 
@@ -20,25 +18,6 @@ namespace mftx {
 
 constexpr int QT = 256;          // threads per block
 constexpr int QB_MAX = 1024;     // blocks (= partial min/max pairs) at most
-
-__device__ __forceinline__ void wave_minmax(float &lo, float &hi) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, off));
-        hi = fmaxf(hi, __shfl_xor(hi, off));
-    }
-}
-
-__device__ __forceinline__ void block_minmax(float &lo, float &hi, float *sh /* [2 * QT / 64] */) {
-    wave_minmax(lo, hi);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh[2 * w] = lo; sh[2 * w + 1] = hi; }
-    __syncthreads();
-    lo = sh[0]; hi = sh[1];
-#pragma unroll
-    for (int i = 1; i < QT / 64; ++i) { lo = fminf(lo, sh[2 * i]); hi = fmaxf(hi, sh[2 * i + 1]); }
-    __syncthreads();
-}
 
 __global__ __launch_bounds__(QT) void minmax_partial_kernel(const float *__restrict__ x, long long n,
                                                             float *__restrict__ partial) {
@@ -53,7 +32,7 @@ __global__ __launch_bounds__(QT) void minmax_partial_kernel(const float *__restr
     }
     if (blockIdx.x == 0)
         for (long long i = (n4 << 2) + threadIdx.x; i < n; i += QT) { lo = fminf(lo, x[i]); hi = fmaxf(hi, x[i]); }
-    block_minmax(lo, hi, sh);
+    block_minmax<QT>(lo, hi, sh);
     if (threadIdx.x == 0) { partial[2 * blockIdx.x] = lo; partial[2 * blockIdx.x + 1] = hi; }
 }
 
@@ -63,39 +42,32 @@ __global__ __launch_bounds__(QT) void quantize_kernel(const float *__restrict__ 
     __shared__ float sh[2 * QT / 64];
     float lo = FLT_MAX, hi = -FLT_MAX;
     for (int i = threadIdx.x; i < n_partial; i += QT) { lo = fminf(lo, partial[2 * i]); hi = fmaxf(hi, partial[2 * i + 1]); }
-    block_minmax(lo, hi, sh);
+    block_minmax<QT>(lo, hi, sh);
     if (blockIdx.x == 0 && threadIdx.x == 0) { lohi[0] = lo; lohi[1] = hi; }
-    const float range = hi - lo;
-    const bool flat = fabsf(range) < 1e-8f;
-    auto enc = [&](float v) -> unsigned short {
-        if (flat) return 0;
-        const float u = (v - lo) / range;
-        return (unsigned short)rintf(u * 65535.f);
-    };
+    const QuantU16 qu = QuantU16::of(lo, hi);
     const long long n4 = n >> 2;
     const float4 *x4 = reinterpret_cast<const float4 *>(x);
     ushort4 *q4 = reinterpret_cast<ushort4 *>(q);
     for (long long i = (long long)blockIdx.x * QT + threadIdx.x; i < n4; i += (long long)gridDim.x * QT) {
         const float4 v = x4[i];
-        q4[i] = make_ushort4(enc(v.x), enc(v.y), enc(v.z), enc(v.w));
+        q4[i] = make_ushort4(qu.enc(v.x), qu.enc(v.y), qu.enc(v.z), qu.enc(v.w));
     }
     if (blockIdx.x == 0)
-        for (long long i = (n4 << 2) + threadIdx.x; i < n; i += QT) q[i] = enc(x[i]);
+        for (long long i = (n4 << 2) + threadIdx.x; i < n; i += QT) q[i] = qu.enc(x[i]);
 }
 
 __global__ __launch_bounds__(QT) void dequantize_kernel(const unsigned short *__restrict__ q, long long n, float lo,
                                                         float hi, float *__restrict__ x) {
-    const float range = hi - lo;
-    auto dec = [&](unsigned short v) { return ((float)v / 65535.f) * range + lo; };
+    const QuantU16 qu = QuantU16::of(lo, hi);
     const long long n4 = n >> 2;
     const ushort4 *q4 = reinterpret_cast<const ushort4 *>(q);
     float4 *x4 = reinterpret_cast<float4 *>(x);
     for (long long i = (long long)blockIdx.x * QT + threadIdx.x; i < n4; i += (long long)gridDim.x * QT) {
         const ushort4 v = q4[i];
-        x4[i] = make_float4(dec(v.x), dec(v.y), dec(v.z), dec(v.w));
+        x4[i] = make_float4(qu.dec(v.x), qu.dec(v.y), qu.dec(v.z), qu.dec(v.w));
     }
     if (blockIdx.x == 0)
-        for (long long i = (n4 << 2) + threadIdx.x; i < n; i += QT) x[i] = dec(q[i]);
+        for (long long i = (n4 << 2) + threadIdx.x; i < n; i += QT) x[i] = qu.dec(q[i]);
 }
 
 static int blocks_for(long long n) {

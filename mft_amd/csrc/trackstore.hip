@@ -6,7 +6,7 @@
 //            channels in one pass; then every block re-reduces the partials (as quantize_kernel does) and quantises its pixels.
 //            Per channel bitwise mftx_quantize_u16 of that plane alone: min and max do not depend on the order they are taken in.
 //   unpack : packed + lohi -> planes, per channel bitwise mftx_dequantize_u16 (lo, hi read from device memory).
-//   query  : chain.hip's sample_points_kernel, its taps dequantised with dequantize_kernel's dec() -- an out-of-frame tap is 0,
+//   query  : chain.hip's sample_points_kernel, its taps dequantised with QuantU16::dec -- an out-of-frame tap is 0,
 //            not dec(0) = lo.  Bitwise mftx_sample_points on the unpacked planes.
 //   locate : the inverse -- points given ON stored frames -> the template points they are the images of: a search over the
 //            template's cells (bilinear patches solved by Newton steps, the winner a 64-bit integer atomic minimum) and a resolve
@@ -20,17 +20,22 @@
 //   flow_from_best : the same with every entry that holds the source frame a candidate: per (pixel, column) the candidate whose
 //            chained result has the smallest (occluded, sigma, rank) wins -- a 64-bit integer minimum in registers, one launch.
 //
-// Shared between them: TsSampler (query, flow_from: the bilinear sampler set up once per point, its taps' loads and their
-// weighted sum), ts_cell_tile (locate's search, the scatter: a tile's corners staged and the lane's InvCell), ts_solve_cell /
-// ts_mix / ts_locate_key (search, scatter, both resolves), and on the host ts_cell_grids / ts_launch_inverse.
+// Shared with codec.hip: quant_u16.h (block_minmax, QuantU16's enc and dec).  Shared with chain.hip: grid_sample.h (the sampler's
+// coordinate round trip, weights, order of summation, clamped taps; the host's grid_scales).
+// Shared between the kernels here: TsSampler (query, flow_from, flow_from_best: grid_sample.h's sampler set up once per point, its
+// taps' loads and their dequantised blend), ts_chain_behind (flow_from, flow_from_best: the chaining rule), ts_cell_tile (locate's search, the scatter: a tile's corners staged
+// and the lane's InvCell), ts_solve_cell / ts_mix / ts_locate_key (search, scatter, both resolves), and on the host ts_cell_grids /
+// ts_launch_inverse.
 //
 // Planes are read and written one float per lane (four pixels per thread in flight): their bases need 4-byte alignment only
 // (flow y of a [2][H][W] tensor and the planes of a [4][H][W] buffer sit H * W floats apart, which is no multiple of 16
 // bytes when H * W % 4 != 0).
-// Compiled like chain.o: -ffp-contract=off (the float arithmetic is the reference's, operation by operation),
+// Compiled like chain.o: -ffp-contract=off (the float arithmetic rounds as the two headers write it),
 // -fno-slp-vectorize and no packed-fp32 instructions (EXEC-masked loads and stores next to the sampler's arithmetic).
 #include "common.h"
+#include "grid_sample.h"
 #include "profile.h"
+#include "quant_u16.h"
 #include <cfloat>
 
 namespace mftx {
@@ -41,21 +46,6 @@ constexpr int TS_PX = 4;            // pixels per thread and pass (and what size
 
 struct Frame4 { const float *p[4]; };        // flow x, flow y, occlusion, sigma: [H * W] each
 struct Frame4Out { float *p[4]; };
-
-__device__ __forceinline__ void ts_block_minmax(float &lo, float &hi, float *sh /* [2 * TS_T / 64] */) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, off));
-        hi = fmaxf(hi, __shfl_xor(hi, off));
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh[2 * w] = lo; sh[2 * w + 1] = hi; }
-    __syncthreads();
-    lo = sh[0]; hi = sh[1];
-#pragma unroll
-    for (int i = 1; i < TS_T / 64; ++i) { lo = fminf(lo, sh[2 * i]); hi = fmaxf(hi, sh[2 * i + 1]); }
-    __syncthreads();
-}
 
 // partial: [gridDim.x][4][2] = (min, max) of each channel over the block's pixels
 __device__ __forceinline__ void ts_minmax_body(const Frame4 &f, long long n, float *__restrict__ partial, float *sh) {
@@ -86,7 +76,7 @@ __device__ __forceinline__ void ts_minmax_body(const Frame4 &f, long long n, flo
     }
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        ts_block_minmax(lo[c], hi[c], sh);
+        block_minmax<TS_T>(lo[c], hi[c], sh);
         if (threadIdx.x == 0) {
             partial[8 * (long long)blockIdx.x + 2 * c] = lo[c];
             partial[8 * (long long)blockIdx.x + 2 * c + 1] = hi[c];
@@ -101,8 +91,7 @@ __global__ __launch_bounds__(TS_T) void ts_minmax_kernel(Frame4 f, long long n, 
 
 __device__ __forceinline__ void ts_pack_body(const Frame4 &f, long long n, const float *__restrict__ partial, int n_partial,
                                              ushort4 *__restrict__ packed, float *__restrict__ lohi, float *sh) {
-    float lo[4], range[4];
-    bool flat[4];
+    QuantU16 qu[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         float l = FLT_MAX, h = -FLT_MAX;
@@ -110,18 +99,11 @@ __device__ __forceinline__ void ts_pack_body(const Frame4 &f, long long n, const
             l = fminf(l, partial[8 * i + 2 * c]);
             h = fmaxf(h, partial[8 * i + 2 * c + 1]);
         }
-        ts_block_minmax(l, h, sh);
+        block_minmax<TS_T>(l, h, sh);
         if (blockIdx.x == 0 && threadIdx.x == 0) { lohi[2 * c] = l; lohi[2 * c + 1] = h; }
-        lo[c] = l;
-        range[c] = h - l;
-        flat[c] = fabsf(range[c]) < 1e-8f;
+        qu[c] = QuantU16::of(l, h);
     }
-    // quantize_kernel's enc(), per channel
-    auto enc = [&](int c, float v) -> unsigned short {
-        if (flat[c]) return 0;
-        const float u = (v - lo[c]) / range[c];
-        return (unsigned short)rintf(u * 65535.f);
-    };
+    auto enc4 = [&](float x, float y, float z, float w) { return make_ushort4(qu[0].enc(x), qu[1].enc(y), qu[2].enc(z), qu[3].enc(w)); };
     const long long stride = (long long)gridDim.x * TS_T;
     long long i = (long long)blockIdx.x * TS_T + threadIdx.x;
     for (; i + (TS_PX - 1) * stride < n; i += TS_PX * stride) {
@@ -132,10 +114,10 @@ __device__ __forceinline__ void ts_pack_body(const Frame4 &f, long long n, const
             for (int c = 0; c < 4; ++c) v[u][c] = f.p[c][i + u * stride];
 #pragma unroll
         for (int u = 0; u < TS_PX; ++u)
-            packed[i + u * stride] = make_ushort4(enc(0, v[u][0]), enc(1, v[u][1]), enc(2, v[u][2]), enc(3, v[u][3]));
+            packed[i + u * stride] = enc4(v[u][0], v[u][1], v[u][2], v[u][3]);
     }
     for (; i < n; i += stride)
-        packed[i] = make_ushort4(enc(0, f.p[0][i]), enc(1, f.p[1][i]), enc(2, f.p[2][i]), enc(3, f.p[3][i]));
+        packed[i] = enc4(f.p[0][i], f.p[1][i], f.p[2][i], f.p[3][i]);
 }
 
 __global__ __launch_bounds__(TS_T) void ts_pack_kernel(Frame4 f, long long n, const float *__restrict__ partial, int n_partial,
@@ -166,16 +148,15 @@ __global__ __launch_bounds__(TS_T) void ts_pack_multi_kernel(MultiFrameSet fs, l
     ts_pack_body(f, n, partial + 8 * (long long)blockIdx.y * gridDim.x, (int)gridDim.x, m.packed, m.lohi, sh);
 }
 
-// dequantize_kernel's dec() for the four channels of one packed pixel
+// the four channels of one packed pixel dequantised, (lo, hi) per channel from a lohi table
 struct Dec4 {
-    float lo[4], range[4];
+    QuantU16 qu[4];
     __device__ __forceinline__ explicit Dec4(const float *__restrict__ lohi) {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) { lo[c] = lohi[2 * c]; range[c] = lohi[2 * c + 1] - lohi[2 * c]; }
+        for (int c = 0; c < 4; ++c) qu[c] = QuantU16::of(lohi[2 * c], lohi[2 * c + 1]);
     }
-    __device__ __forceinline__ float one(int c, unsigned v) const { return ((float)v / 65535.f) * range[c] + lo[c]; }
     __device__ __forceinline__ float4 operator()(uint2 q) const {
-        return make_float4(one(0, q.x & 0xffffu), one(1, q.x >> 16), one(2, q.y & 0xffffu), one(3, q.y >> 16));
+        return make_float4(qu[0].dec(q.x & 0xffffu), qu[1].dec(q.x >> 16), qu[2].dec(q.y & 0xffffu), qu[3].dec(q.y >> 16));
     }
 };
 
@@ -188,36 +169,26 @@ __global__ __launch_bounds__(TS_T) void ts_unpack_kernel(const uint2 *__restrict
     }
 }
 
-// chain.hip's sample_points_kernel sampler at one point (px, py) of an H x W frame, set up once and used on any number of stored
-// frames.  The four taps' addresses are clamped into the frame so that their loads are unconditional -- a caller issues the
-// loads of several frames before the first mix(), and they are all in flight together instead of one bounds-tested gather
-// after the other; a tap outside the frame counts as 0 in mix().
+// grid_sample.h's sampler at one point (px, py) of an H x W frame, set up once and used on any number of stored frames.  The
+// four taps' addresses are clamped into the frame so that their loads are unconditional -- a caller issues the loads of several
+// frames before the first mix(), and they are all in flight together instead of one bounds-tested gather after the other; a
+// tap outside the frame counts as 0 in mix().
 struct TsSampler {
-    float w00, w01, w10, w11;
-    bool inx0, inx1, iny0, iny1;
-    long long o00, o01, o10, o11;
+    Bilinear w;
+    ClampedTaps t;
     __device__ __forceinline__ TsSampler(float px, float py, float sx, float sy, int H, int W) {
-        const float ix = ((px * sx - 1.f) + 1.f) / 2.f * (float)(W - 1);
-        const float iy = ((py * sy - 1.f) + 1.f) / 2.f * (float)(H - 1);
-        const float flx = floorf(ix), fly = floorf(iy);
-        const float wx = ix - flx, wy = iy - fly;
-        const int x0 = (int)fminf(fmaxf(flx, -1.0e6f), 1.0e6f);
-        const int y0 = (int)fminf(fmaxf(fly, -1.0e6f), 1.0e6f);
-        w00 = (1.f - wx) * (1.f - wy); w01 = wx * (1.f - wy); w10 = (1.f - wx) * wy; w11 = wx * wy;
-        inx0 = x0 >= 0 && x0 < W; inx1 = x0 + 1 >= 0 && x0 + 1 < W; iny0 = y0 >= 0 && y0 < H; iny1 = y0 + 1 >= 0 && y0 + 1 < H;
-        const int cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x0 + 1, 0), W - 1), cy0 = min(max(y0, 0), H - 1), cy1 = min(max(y0 + 1, 0), H - 1);
-        o00 = (long long)cy0 * W + cx0; o01 = (long long)cy0 * W + cx1; o10 = (long long)cy1 * W + cx0; o11 = (long long)cy1 * W + cx1;
+        const GridSample s = grid_sample_at(px, py, sx, sy, H, W);
+        w = s.w;
+        t = clamped_taps(s, H, W);
     }
     __device__ __forceinline__ void load(const uint2 *__restrict__ frame, uint2 (&q)[4]) const {
-        q[0] = frame[o00]; q[1] = frame[o01]; q[2] = frame[o10]; q[3] = frame[o11];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = frame[t.o[k]];
     }
-    // (flow x, flow y, occlusion, sigma) at the point: the taps dequantised, in sample_points_kernel's order of summation
+    // (flow x, flow y, occlusion, sigma) at the point: the taps dequantised, then blended
     __device__ __forceinline__ float4 mix(const Dec4 &dec, const uint2 (&q)[4]) const {
         const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-        const float4 t00 = iny0 && inx0 ? dec(q[0]) : zero, t01 = iny0 && inx1 ? dec(q[1]) : zero;
-        const float4 t10 = iny1 && inx0 ? dec(q[2]) : zero, t11 = iny1 && inx1 ? dec(q[3]) : zero;
-        return make_float4(t00.x * w00 + t01.x * w01 + t10.x * w10 + t11.x * w11, t00.y * w00 + t01.y * w01 + t10.y * w10 + t11.y * w11,
-                           t00.z * w00 + t01.z * w01 + t10.z * w10 + t11.z * w11, t00.w * w00 + t01.w * w01 + t10.w * w10 + t11.w * w11);
+        return w.blend(t.in(0) ? dec(q[0]) : zero, t.in(1) ? dec(q[1]) : zero, t.in(2) ? dec(q[2]) : zero, t.in(3) ? dec(q[3]) : zero);
     }
 };
 
@@ -320,11 +291,8 @@ __device__ __forceinline__ bool ts_solve_cell(const LocCell &c, float qx, float 
     return finite && fabsf(rx) <= TL_EPS && fabsf(ry) <= TL_EPS;
 }
 
-// the sampler's four weights and its order of summation
-__device__ __forceinline__ float ts_mix(float a, float b, float c, float d, float u, float v) {
-    const float w00 = (1.f - u) * (1.f - v), w01 = u * (1.f - v), w10 = (1.f - u) * v, w11 = u * v;
-    return a * w00 + b * w01 + c * w10 + d * w11;
-}
+// the sampler's four weights and its order of summation at the patch's solution (u, v)
+__device__ __forceinline__ float ts_mix(float a, float b, float c, float d, float u, float v) { return Bilinear::at(u, v).blend(a, b, c, d); }
 
 __device__ __forceinline__ unsigned long long ts_locate_key(float occl, float sigma, float thr, unsigned cell) {
     const float s = sigma > 0.f ? sigma : 0.f;
@@ -586,6 +554,18 @@ __global__ __launch_bounds__(256) void ts_atlas_resolve_kernel(const uint2 *cons
 constexpr int TF_FW = 4;            // columns whose taps a lane keeps in flight
 constexpr int TF_COLS = 16;         // columns per workgroup unless the caller says otherwise
 
+// The chaining rule of DenseTrackStore.results_from: src = (Px, Py, occlusion, sigma) of the inverse at pixel (x, y), m the
+// template's stored result sampled at (Px, Py) -> flow x, flow y, occlusion, sigma of the pixel.  Query's row, (Px + m.x,
+// Py + m.y, m.z, m.w), chained behind the inverse.  The maximum keeps a NaN of either operand, as torch.maximum does (fmaxf drops
+// it).  The root is taken in float64 and rounded once, as results_from takes it: the float32 sum is exact in float64, its
+// float64 root is correctly rounded, and because 53 >= 2 * 24 + 2 rounding that once more gives the correctly rounded float32
+// root -- whatever this unit's float32 sqrtf is compiled to.
+__device__ __forceinline__ float4 ts_chain_behind(const float4 &src, const float4 &m, float x, float y) {
+    const float qx = src.x + m.x, qy = src.y + m.y, od = m.z, sd = m.w;
+    const float ss = src.w * src.w + sd * sd;
+    return make_float4(qx - x, qy - y, src.z != src.z ? src.z : (od != od ? od : fmaxf(src.z, od)), (float)sqrt((double)ss));
+}
+
 __global__ __launch_bounds__(256) void ts_flow_from_kernel(const float4 *__restrict__ table, const int *__restrict__ entry,
                                                            const int *__restrict__ row_of, const uint2 *const *__restrict__ frames,
                                                            const float *const *__restrict__ lohis, int n_ranks, int R, int T, int cols,
@@ -634,17 +614,8 @@ __global__ __launch_bounds__(256) void ts_flow_from_kernel(const float4 *__restr
 #pragma unroll
         for (int u = 0; u < TF_FW; ++u) {
             if (t + u >= t1) continue;
-            const float4 m = smp.mix(Dec4(l[u]), q[u]);
-            // query's row ...
-            const float qx = src.x + m.x, qy = src.y + m.y, od = m.z, sd = m.w;
-            // ... chained behind the inverse.  The maximum keeps a NaN of either operand, as torch.maximum does (fmaxf drops it).
-            // The root is taken in float64 and rounded once, as DenseTrackStore.results_from takes it: the float32 sum is exact in
-            // float64, its float64 root is correctly rounded, and because 53 >= 2 * 24 + 2 rounding that once more gives the
-            // correctly rounded float32 root -- whatever this unit's float32 sqrtf is compiled to.
-            const float ss = src.w * src.w + sd * sd;
-            float fx = qx - x, fy = qy - y;
-            float oc = src.z != src.z ? src.z : (od != od ? od : fmaxf(src.z, od));
-            float sg = (float)sqrt((double)ss);
+            const float4 r = ts_chain_behind(src, smp.mix(Dec4(l[u]), q[u]), x, y);
+            float fx = r.x, fy = r.y, oc = r.z, sg = r.w;
             if (!ok[u]) { fx = nan; fy = nan; oc = 1.f; sg = inf; }
             const long long c = t + u;
             flow[2 * c * n + p] = fx;
@@ -732,13 +703,8 @@ __global__ __launch_bounds__(256) void ts_flow_best_kernel(const float4 *__restr
 #pragma unroll
             for (int u = 0; u < TF_FW; ++u) {
                 if (!ok[u]) continue;
-                const float4 m = smp.mix(Dec4(l[u]), q[u]);
-                // chained exactly as ts_flow_from_kernel chains (the NaN-keeping maximum and the float64 root: see there)
-                const float qx = src.x + m.x, qy = src.y + m.y, od = m.z, sd = m.w;
-                const float ss = src.w * src.w + sd * sd;
-                const float fx = qx - x, fy = qy - y;
-                const float oc = src.z != src.z ? src.z : (od != od ? od : fmaxf(src.z, od));
-                const float sg = (float)sqrt((double)ss);
+                const float4 r = ts_chain_behind(src, smp.mix(Dec4(l[u]), q[u]), x, y);
+                const float fx = r.x, fy = r.y, oc = r.z, sg = r.w;
                 const unsigned field = sg != sg ? 0x7fffffffu : (sg > 0.f ? __float_as_uint(sg) : 0u);
                 const unsigned long long key = ((unsigned long long)(oc <= thr ? 0u : 1u) << 39) | ((unsigned long long)field << 8) | rank;
                 if (key < best[u]) { best[u] = key; bx[u] = fx; by[u] = fy; bo[u] = oc; bs[u] = sg; }
@@ -893,8 +859,8 @@ extern "C" int mftx_trackstore_query(const uint16_t *const *chunks, const float 
                     (long long)column0 + T - 1);
     if (!aligned16(table)) return fail(MFTX_E_ALIGN, "trackstore_query: the table must be 16-byte aligned");
     if (!aligned_to(slots, 4) || !aligned_to(xy, 4)) return fail(MFTX_E_ALIGN, "trackstore_query: slots and xy must be 4-byte aligned");
-    // np.array([2/(W-1), 2/(H-1)]).astype(np.float32)  (double division, then rounded): chain.hip's scales()
-    const float sx = (float)(2.0 / (double)(W - 1)), sy = (float)(2.0 / (double)(H - 1));
+    float sx, sy;
+    grid_scales(H, W, sx, sy);
     // per (point, frame): 4 taps of 8 B, one table entry of 16 B
     ProfScope prof(PC_CHAIN, (hipStream_t)stream, (32.0 + 16.0) * (double)N * (double)T);
     for (int c0 = 0; c0 < n_chunks; c0 += TQ_CHUNKS) {
@@ -1017,8 +983,8 @@ extern "C" int mftx_trackstore_flow_from(const float *table, const int *entry, c
         return fail(MFTX_E_ALIGN, "trackstore_flow_from: the pointer tables frames and lohis must be 8-byte aligned");
     for (const auto &a : ptrs)
         if (!aligned_to(a.p, 4)) return fail(MFTX_E_ALIGN, "trackstore_flow_from: %s must be 4-byte aligned", a.name);
-    // np.array([2/(W-1), 2/(H-1)]).astype(np.float32), as mftx_trackstore_query has them
-    const float sx = (float)(2.0 / (double)(W - 1)), sy = (float)(2.0 / (double)(H - 1));
+    float sx, sy;
+    grid_scales(H, W, sx, sy);
     hipStream_t s = (hipStream_t)stream;
     // per pixel and column block: a table row and an entry; per pixel and column: two pointers, a lohi table (shared between the
     // lanes of one winner), 4 taps of 8 B, 16 B of results
@@ -1054,7 +1020,8 @@ extern "C" int mftx_trackstore_flow_from_best(const float *tables, const int *ce
         return fail(MFTX_E_ALIGN, "trackstore_flow_from_best: the pointer tables frames and lohis must be 8-byte aligned");
     for (const auto &a : ptrs)
         if (!aligned_to(a.p, 4)) return fail(MFTX_E_ALIGN, "trackstore_flow_from_best: %s must be 4-byte aligned", a.name);
-    const float sx = (float)(2.0 / (double)(W - 1)), sy = (float)(2.0 / (double)(H - 1));      // as mftx_trackstore_query has them
+    float sx, sy;
+    grid_scales(H, W, sx, sy);
     hipStream_t s = (hipStream_t)stream;
     // per pixel, candidate and group of TF_FW columns: a row and a cell; per pixel, column and candidate (at most): 4 taps of 8 B; per
     // pixel and column: 20 B of results

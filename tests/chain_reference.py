@@ -28,7 +28,7 @@ def _f32(a):
 
 
 def unnormalised(p, size):
-    """Pixel coordinate -> normalised -> pixel coordinate, in float32 (chain.hip, ``chain_px``)."""
+    """Pixel coordinate -> normalised -> pixel coordinate, in float32 (csrc/grid_sample.h, ``grid_sample_at``)."""
     p = _f32(p)
     s = F32(2 / (size - 1))
     return ((p * s - F32(1)) + F32(1)) / F32(2) * F32(size - 1)

@@ -54,9 +54,11 @@ WHERE EACH PATH IS COVERED
   * warp_backward_kernel: C in {1, 2, 3, 5} at 2 x 2, 7 x 259, 37 x 53, every channel.
   * convex_upsample_kernel: P in {1, 3} x ld_ou in {3, 4, 7} x (h, w) in {(1, 1), (1, 5), (4, 1), (3, 4)} x pads in
     {(0, 0, 0, 0), (3, 4, 3, 4)}, planar and packed.
+  * one sampler across sample_points_kernel, warp_backward_kernel and chain_kernel (csrc/grid_sample.h): bit for bit on one right
+    result at 5 x 7 and 37 x 53, every class of ``_point_kinds`` among the destinations.
 
 None of these inputs can produce an out-of-range address: the clamps of the tap coordinates precede the int cast, ``tap()`` checks
-bounds before it reads and ``packed_tap()`` clamps the address.  These are value tests."""
+bounds before it reads and ``clamped_tap()`` (under ``packed_tap()``) clamps the address.  These are value tests."""
 import numpy as np
 import pytest
 import torch
@@ -285,6 +287,64 @@ def test_warp_backward(ops, C, H, W):
         assert u <= BOUND, (c, u)
     if H * W > 100:
         assert (~np.isfinite(ref)).any() and (np.isfinite(ref) & (ref != 0)).mean() > 0.25
+
+
+# ---------------------------------------------------------------------------
+# one sampler across the kernels
+# ---------------------------------------------------------------------------
+
+def _same_or_both_nan(got, want, what):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, what
+    nan = np.isnan(got) | np.isnan(want)
+    assert np.array_equal(np.isnan(got), np.isnan(want)), (what, "NaN pattern")
+    bad = (cr.bits(got) != cr.bits(want)) & ~nan
+    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist())
+
+
+@pytest.mark.parametrize("H,W", [(5, 7), (37, 53)])
+def test_one_sampler_across_kernels(ops, H, W):
+    """``sample_points``, ``warp_backward`` and ``chain`` sample one right result R at the same destinations g + flow and must
+    give the same bits: they share one sampler (csrc/grid_sample.h).  The destinations cover every class of ``_point_kinds``;
+    R holds NaN and +inf.  Compared as int32; where one side is NaN only "both are NaN" is asserted.  (The track store's query is
+    tied to ``sample_points`` by tests/test_gpu_trackstore.py.)  Sigma of ``chain`` is not compared: sqrt(sr * sr) is not sr."""
+    rng = np.random.default_rng([11, H, W])
+    R = cr.make_result(rng, H, W, 3.0, False, True)
+    flow = cr.make_result(rng, H, W, 3.0, True, False)[0]
+    gx, gy = cr._grid(H, W)
+    kinds = _point_kinds(H, W)
+    n = len(kinds)
+    assert n <= H * W
+    flat = flow.reshape(2, -1)
+    flat[0, :n] = kinds[:, 0] - gx.reshape(-1)[:n]
+    flat[1, :n] = kinds[:, 1] - gy.reshape(-1)[:n]
+    px, py = gx + flow[0], gy + flow[1]                                # float32: the one IEEE addition the kernels do
+    assert px.dtype == np.float32 and py.dtype == np.float32
+    assert np.array_equal(np.stack([px.reshape(-1)[:n], py.reshape(-1)[:n]], 1), kinds)      # every class is met as written
+    N = H * W
+    # 1: sample_points, the anchor
+    xy = np.stack([px.reshape(-1), py.reshape(-1)], 1)
+    table = torch.zeros((N, 4), device=DEV)
+    ops.sample_points([tuple(dev(a) for a in R)], torch.zeros(N, dtype=torch.int32, device=DEV), dev(xy), table, 0)
+    row = table.cpu().numpy().reshape(H, W, 4)
+    s_occl, s_sigma = row[..., 2], row[..., 3]
+    # 2: warp_backward of the stacked planes (occlusion, sigma)
+    warped = ops.warp_backward(dev(flow), dev(np.concatenate([R[1], R[2]], 0))).cpu().numpy()
+    _same_or_both_nan(warped[0], s_occl, "warp_backward, occlusion plane")
+    _same_or_both_nan(warped[1], s_sigma, "warp_backward, sigma plane")
+    # 3: chain behind a left result that leaves the right one as it is (max(-inf, o) = o)
+    L = (flow, np.full((1, H, W), -np.inf, np.float32), np.zeros((1, H, W), np.float32))
+    cflow, coccl, _ = (t.cpu().numpy() for t in ops.chain(tuple(dev(a) for a in L), tuple(dev(a) for a in R)))
+    _same_or_both_nan(coccl[0], s_occl, "chain, occlusion")
+    with np.errstate(invalid="ignore", over="ignore"):
+        want_fx, want_fy = row[..., 0] - gx, row[..., 1] - gy
+    assert want_fx.dtype == np.float32
+    _same_or_both_nan(cflow[0], want_fx, "chain, flow x")
+    _same_or_both_nan(cflow[1], want_fy, "chain, flow y")
+    # the inputs do exercise the sampler: taps inside and outside, and non-finite samples at the larger size
+    assert (s_sigma == 0).any() and (np.isfinite(s_sigma) & (s_sigma != 0)).any()
+    if H * W > 100:
+        assert np.isnan(s_sigma).any() and np.isposinf(s_sigma).any()
 
 
 # ---------------------------------------------------------------------------
