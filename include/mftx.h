@@ -743,6 +743,40 @@ int mftx_trackstore_flow_from_best(const float *tables, const int *cells, const 
                                    float occlusion_threshold, int columns_per_block, float *flow, float *occl, float *sigma,
                                    int *entry, void *stream);
 
+/* The same choice for sparse POINTS given on any number of source frames: per (point, column) the candidate with the smallest key.
+ * Step A is the caller's: mftx_trackstore_locate with the points sorted by source frame ("group") and repeated per candidate --
+ * every entry that holds the group's frame, ascending rank -- its rows kept un-reduced.  DEVICE memory throughout:
+ *   located [Q][4] float32 (16-byte aligned) and cells [Q] int32: step A's rows, group after group and within a group of n points
+ *   candidate after candidate (row = the group's first row + k * n + i): candidate k's template point (Px, Py), occlusion and sigma
+ *   there, and the cell, < 0 = this candidate does not find the point;
+ *   tiles [n_tiles][2] int32: (group, first point of the tile within its group) -- a group's points cut into tiles of at most 64, so
+ *   that a tile never holds points of two source frames;
+ *   groups [G][5] int32: (first row of step A, points n, first sorted point, first candidate, one past its last candidate);
+ *   rank_of [C] / row_of [C] int32: per candidate of any group its rank (0 .. 255), what `entry` reports, and its row of the pointer
+ *   tables; order [N] int32: sorted point -> the caller's row;
+ *   frames [R * T] / lohis [R * T]: as for mftx_trackstore_flow_from, NULL = that row's template does not cover the column;
+ *   table [N][T][4] float32 (16-byte aligned) and entry [N][T] int32: the results.
+ * max_candidates: the largest candidate count of a group, at most 256.
+ * Candidate k has an answer for point i and column t iff its cell is >= 0, 0 <= row_of[k] < R and the pointers of (row_of[k], t) are
+ * not NULL: the frame sampled at (Px, Py) exactly as mftx_trackstore_query samples it -- (qx, qy, o_dst, s_dst) -- chained as
+ * mftx_trackstore_flow_from chains, with the position in the place of the flow:
+ *   (qx, qy, max(o_src, o_dst) with a NaN of either kept, sqrt(s_src^2 + s_dst^2) correctly rounded).
+ * Among the candidates that have one the smallest key of mftx_trackstore_flow_from_best wins, unchanged; its four values go to the
+ * caller's row of `table` and its rank to `entry`; where no candidate has an answer: NaN, NaN, 1, +inf and -1.
+ * ONE launch: tiles x column blocks of columns_per_block columns (0: the default, 16).  Each of a workgroup's four waves takes every
+ * fourth column with its lanes over the points and walks the candidates in order with the running minimum in registers (a 64-bit
+ * integer compare, no atomics); the winners leave through LDS transposed, in 256-byte runs of `table` and 64-byte runs of `entry`.
+ * Every output element is written exactly once and nothing else is written; the results do not depend on columns_per_block.  An
+ * index of a table that is not inside the table it points into reads nothing.  No allocation, no copy, no synchronisation.
+ * MFTX_E_ARG: a negative count, H or W < 2, max_candidates > 256, more than 65535 column blocks, a null pointer;
+ * MFTX_E_ALIGN: a misaligned table.  N == 0 or T == 0: nothing is done, 0 is returned.  C == 0: every result is the fill, and
+ * located .. lohis are not looked at. */
+int mftx_trackstore_tracks_from_best(const float *located, const int *cells, const int *tiles, const int *groups,
+                                     const int *rank_of, const int *row_of, const int *order, const uint16_t *const *frames,
+                                     const float *const *lohis, int n_tiles, int G, int C, int max_candidates, int Q, int N, int R,
+                                     int T, int H, int W, float occlusion_threshold, int columns_per_block, float *table, int *entry,
+                                     void *stream);
+
 /* ---- 8f-4: frame / result transport without copy queues -------------------------------------------------------------------
  * A copy KERNEL: src -> dst, n bytes, both 16-byte aligned; either may be PINNED HOST memory (hipHostMalloc / torch
  * pin_memory: mapped into the device's address space), which a kernel reads and writes over PCIe directly.  Unlike

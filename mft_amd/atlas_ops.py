@@ -1,7 +1,8 @@
-"""Torch-tensor front end of the track atlas's per-(pixel, column) read-out (``mftx_trackstore_flow_from_best``), by the contract of
-mft_amd/ops.py: device / dtype / contiguity checked, raw device pointers and the current HIP stream passed, ``MftxError`` on a
-non-zero return.  The host tables go up through ``ops._upload_tables``; stream ordering is held by
-tests/test_gpu_track_atlas_best.py."""
+"""Torch-tensor front end of the track atlas's per-(pixel, column) and per-(point, column) read-outs
+(``mftx_trackstore_flow_from_best``, ``mftx_trackstore_tracks_from_best``), by the contract of mft_amd/ops.py: device / dtype /
+contiguity checked, raw device pointers and the current HIP stream passed, ``MftxError`` on a non-zero return.  The host tables go
+up through ``ops._upload_tables``; stream ordering is held by tests/test_gpu_track_atlas_best.py and
+tests/test_gpu_track_atlas_points.py."""
 from __future__ import annotations
 
 import numpy as np
@@ -12,6 +13,8 @@ from ._lib import MftxError, check
 
 TRACKSTORE_BEST_COLUMNS = 16             # columns per workgroup of mftx_trackstore_flow_from_best unless the caller says otherwise
 TRACKSTORE_BEST_ENTRIES = 256            # candidates per call (8 bits of its key)
+TRACKSTORE_POINTS_COLUMNS = 16           # columns per workgroup of mftx_trackstore_tracks_from_best unless the caller says otherwise
+TRACKSTORE_POINTS_TILE = 64              # points per tile of that kernel: a wave's lanes
 
 
 def trackstore_flow_from_best(tables, cells, rank_of, row_of, frame_ptrs, lohi_ptrs, flow, occl, sigma, entry,
@@ -58,3 +61,80 @@ def trackstore_flow_from_best(tables, cells, rank_of, row_of, frame_ptrs, lohi_p
     check(lib.mftx_trackstore_flow_from_best(tp, cp, ranks, rows, frames, lohis, E, R, T, H, W, float(occlusion_threshold),
                                              int(columns_per_block), fp, op, sp, ep, ops._stream()), "mftx_trackstore_flow_from_best")
     return flow, occl, sigma, entry
+
+
+def points_tables(group_sizes, group_candidates):
+    """The tile and group tables of ``mftx_trackstore_tracks_from_best`` for points sorted by source frame: group g has
+    ``group_sizes[g]`` points (>= 1) and ``group_candidates[g]`` candidates; step A's rows run group after group and, within a group,
+    candidate after candidate -> (tiles [n_tiles, 2] = (group, first point within it), groups [G, 5] = (first row, points, first
+    sorted point, first candidate, one past the last candidate), Q, C) as int64 host arrays and two integers."""
+    sizes = np.asarray(group_sizes, dtype=np.int64).reshape(-1)
+    cands = np.asarray(group_candidates, dtype=np.int64).reshape(-1)
+    if sizes.shape != cands.shape or (sizes < 1).any() or (cands < 0).any():
+        raise MftxError("points_tables: a size >= 1 and a candidate count >= 0 per group")
+    rows, cand0 = np.concatenate([[0], np.cumsum(sizes * cands)]), np.concatenate([[0], np.cumsum(cands)])
+    point0 = np.concatenate([[0], np.cumsum(sizes)])
+    groups = np.stack([rows[:-1], sizes, point0[:-1], cand0[:-1], cand0[1:]], axis=1).reshape(-1, 5)
+    tiles = np.asarray([(g, first) for g, n in enumerate(sizes) for first in range(0, int(n), TRACKSTORE_POINTS_TILE)],
+                       dtype=np.int64).reshape(-1, 2)
+    return tiles, groups, int(rows[-1]), int(cand0[-1])
+
+
+def trackstore_tracks_from_best(located, cells, group_sizes, group_candidates, rank_of, row_of, order, frame_ptrs, lohi_ptrs, frame_size,
+                                table, entry, occlusion_threshold=0.5, columns_per_block=0):
+    """Points given on any number of source frames followed over T columns, the candidate chosen per point and column, in one call
+    (``mftx_trackstore_tracks_from_best``).  The N points are SORTED by source frame into G groups of ``group_sizes`` points;
+    group g has ``group_candidates[g]`` candidates.  located (float32 device [Q, 4]) and cells (int32 device [Q]): the un-reduced
+    rows of ``ops.trackstore_locate_frames`` with the points repeated per candidate -- group after group, within a group candidate
+    after candidate; rank_of / row_of: HOST integers per candidate of every group, in that order; order: N HOST integers, sorted
+    point -> row of the results; frame_ptrs / lohi_ptrs: HOST int64 [R, T] as for ``ops.trackstore_flow_from``; frame_size: (H, W) of
+    the stored frames.  ``table`` (float32
+    device [N, T, 4]) and ``entry`` (int32 device [N, T]) receive per point and column (x, y, chained occlusion, chained sigma) and
+    the rank of the candidate with the smallest key of ``trackstore_flow_from_best``, and NaN, NaN, 1, +inf, -1 where no candidate
+    found the point on a template that covers the column.  A group may have no candidates: its rows are fill.
+    ``columns_per_block``: the columns a workgroup walks (0: TRACKSTORE_POINTS_COLUMNS); the results do not depend on it.  The
+    tables go up through one pinned buffer; no host synchronisation.  Returns (table, entry)."""
+    lib = _lib.load()
+    name = "trackstore_tracks_from_best"
+    tiles, groups, Q, C = points_tables(group_sizes, group_candidates)
+    rank_of = np.asarray(rank_of, dtype=np.int64).reshape(-1)
+    row_of = np.asarray(row_of, dtype=np.int64).reshape(-1)
+    order = np.asarray(order, dtype=np.int64).reshape(-1)
+    frame_ptrs, lohi_ptrs = np.asarray(frame_ptrs, dtype=np.int64), np.asarray(lohi_ptrs, dtype=np.int64)
+    if table.dim() != 3 or int(table.shape[2]) != 4 or tuple(entry.shape) != tuple(table.shape[:2]):
+        raise MftxError(f"{name}: table must be [N, T, 4], entry [N, T]")
+    N, T = int(table.shape[0]), int(table.shape[1])
+    G = int(groups.shape[0])
+    if int(groups[:, 1].sum()) != N or int(order.shape[0]) != N or (N and not np.array_equal(np.sort(order), np.arange(N))):
+        raise MftxError(f"{name}: the groups must hold the N points, and order must name each of the N rows once")
+    if tuple(located.shape) != (Q, 4) or tuple(cells.shape) != (Q,):
+        raise MftxError(f"{name}: located must be [Q, 4] and cells [Q], Q = {Q} rows of the groups' candidates")
+    H, W = (int(s) for s in frame_size)
+    most = int((groups[:, 4] - groups[:, 3]).max()) if G else 0
+    if most > TRACKSTORE_BEST_ENTRIES:
+        raise MftxError(f"{name}: more than {TRACKSTORE_BEST_ENTRIES} candidates in a group")
+    if frame_ptrs.ndim != 2 or frame_ptrs.shape != lohi_ptrs.shape or ((frame_ptrs == 0) != (lohi_ptrs == 0)).any():
+        raise MftxError(f"{name}: frame_ptrs and lohi_ptrs must be [R, T], zero in the same places")
+    R = int(frame_ptrs.shape[0])
+    if int(frame_ptrs.shape[1]) != T:
+        raise MftxError(f"{name}: frame_ptrs and lohi_ptrs must have the table's {T} columns")
+    if int(rank_of.shape[0]) != C or int(row_of.shape[0]) != C:
+        raise MftxError(f"{name}: rank_of and row_of must name a rank and a row for each of the {C} candidates")
+    if C and (R < 1 or row_of.min() < 0 or row_of.max() >= R or rank_of.min() < 0 or rank_of.max() >= TRACKSTORE_BEST_ENTRIES):
+        raise MftxError(f"{name}: rows must be 0 .. R - 1 with R >= 1, ranks 0 .. {TRACKSTORE_BEST_ENTRIES - 1}")
+    if Q > 0x7fffffff:
+        raise MftxError(f"{name}: more than 2^31 - 1 rows")
+    lp, cp = ops._chk(located, "located"), ops._chk(cells, "cells", torch.int32)
+    tp, ep = ops._chk(table, "table"), ops._chk(entry, "entry", torch.int32)
+    if N == 0 or T == 0:          # (empty tensors have no storage to point at)
+        return table, entry
+    small = (tiles.reshape(-1), groups.reshape(-1), order) + ((rank_of, row_of) if C else ())
+    up, addr = ops._upload_tables(table.device, (frame_ptrs.reshape(-1), lohi_ptrs.reshape(-1)) if C else (), small)
+    if C:
+        frames, lohis, tl, gr, od, ranks, rows = addr
+    else:           # (no candidates anywhere: nothing but the tiles and the results is looked at)
+        (tl, gr, od), frames, lohis, ranks, rows, lp, cp = addr, None, None, None, None, None, None
+    check(lib.mftx_trackstore_tracks_from_best(lp, cp, tl, gr, ranks, rows, od, frames, lohis, int(tiles.shape[0]), G, C, most, Q, N, R, T,
+                                               H, W, float(occlusion_threshold), int(columns_per_block), tp, ep, ops._stream()),
+          "mftx_trackstore_tracks_from_best")
+    return table, entry

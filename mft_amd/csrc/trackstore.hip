@@ -19,11 +19,13 @@
 //            the chaining rule of DenseTrackStore.results_from in one launch, straight to planar flow, occlusion and sigma.
 //   flow_from_best : the same with every entry that holds the source frame a candidate: per (pixel, column) the candidate whose
 //            chained result has the smallest (occluded, sigma, rank) wins -- a 64-bit integer minimum in registers, one launch.
+//   tracks_from_best : that choice for sparse points given on any number of source frames, behind locate's un-reduced rows: query's
+//            tiles of 64 points x 16 columns, the candidates of a tile's source frame walked per wave, the winners out through LDS.
 //
 // Shared with codec.hip: quant_u16.h (block_minmax, QuantU16's enc and dec).  Shared with chain.hip: grid_sample.h (the sampler's
 // coordinate round trip, weights, order of summation, clamped taps; the host's grid_scales).
-// Shared between the kernels here: TsSampler (query, flow_from, flow_from_best: grid_sample.h's sampler set up once per point, its
-// taps' loads and their dequantised blend), ts_chain_behind (flow_from, flow_from_best: the chaining rule), ts_cell_tile (locate's search, the scatter: a tile's corners staged
+// Shared between the kernels here: TsSampler (query, flow_from, flow_from_best, tracks_from_best: grid_sample.h's sampler set up once
+// per point, its taps' loads and their dequantised blend), ts_chain_behind (flow_from, flow_from_best, tracks_from_best: the chaining rule), ts_cell_tile (locate's search, the scatter: a tile's corners staged
 // and the lane's InvCell), ts_solve_cell / ts_mix / ts_locate_key (search, scatter, both resolves), and on the host ts_cell_grids /
 // ts_launch_inverse.
 //
@@ -723,6 +725,128 @@ __global__ __launch_bounds__(256) void ts_flow_best_kernel(const float4 *__restr
     }
 }
 
+// ---- tracks_from_best: ts_flow_best_kernel's choice for sparse POINTS, given on any number of source frames --------------------------
+// The sparse sibling of ts_flow_best_kernel in the shape of ts_query_kernel.  Step A (mftx_trackstore_locate, the points repeated per
+// candidate) has left `located` [Q][4] and `cells` [Q]: source frame after source frame ("group") and, within a group of n points and E
+// candidates, candidate after candidate -- row = first row of the group + k * n + i.  The host has sorted the points by source frame
+// and cut every group into tiles of at most TP_P points, so a tile's candidate list is wave-uniform: rank_of, row_of and the frame and
+// lohi pointers of (candidate, column) are scalar loads, and only the cell and the located row are per lane.
+//   tiles  [n_tiles][2]: (group, first point of the tile within its group)
+//   groups [G][5]      : (first row of step A, points, first sorted point, first candidate, one past the last candidate)
+//   order  [N]         : sorted point -> the caller's row
+// A workgroup owns a tile x `cols` columns, walked in chunks of TP_F: each of its four waves takes every fourth column of the chunk
+// with its lanes over the POINTS and, per candidate in order, sets TsSampler up at the candidate's template point, has its TP_FW
+// columns' taps in flight, chains (the pixel is (0, 0): q - 0 is exact), keys and keeps the running minimum and its four values in
+// registers.  The winners go to a padded LDS tile and leave transposed after ONE barrier per chunk (two tiles in turn: a wave that is
+// a chunk ahead writes the other one): 16 consecutive lanes write the 16 consecutive columns of one point, 256-byte runs of
+// table [N][T][4] and 64-byte runs of entry [N][T], at the caller's row.  Every lane reaches every barrier: a lane without a point, a
+// candidate that did not find the point and a column beyond T are predicated.  An index that is not inside its table reads nothing.
+constexpr int TP_P = 64, TP_F = 16, TP_FW = TP_F / 4;
+constexpr int TP_COLS = 16;         // columns per workgroup unless the caller says otherwise
+constexpr int TP_ENTRIES = 256;     // candidates per group (8 bits of the key)
+
+__global__ __launch_bounds__(256) void ts_tracks_best_kernel(const float4 *__restrict__ located, const int *__restrict__ cells,
+                                                             const int *__restrict__ tiles, const int *__restrict__ groups,
+                                                             const int *__restrict__ rank_of, const int *__restrict__ row_of,
+                                                             const int *__restrict__ order, const uint2 *const *__restrict__ frames,
+                                                             const float *const *__restrict__ lohis, int G, int C, int Q, int N, int R,
+                                                             int T, int cols, int H, int W, float sx, float sy, float thr,
+                                                             float4 *__restrict__ table, int *__restrict__ entry) {
+    __shared__ float4 tile[2][TP_P][TP_F + 1];      // (+ 1: the lanes of a wave, 17 x 16 bytes apart, spread over the banks)
+    __shared__ int etile[2][TP_P][TP_F + 1];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long first_col = (long long)blockIdx.y * cols;
+    const int t0 = (int)(first_col < T ? first_col : T), t1 = (int)(first_col + cols < T ? first_col + cols : T);
+    // the tile and its group: block-uniform
+    const int g = tiles[2 * (long long)blockIdx.x], first = tiles[2 * (long long)blockIdx.x + 1];
+    int row0 = 0, n = 0, point0 = 0, c0 = 0, c1 = 0;
+    if (g >= 0 && g < G) {
+        const int *gr = groups + 5 * (long long)g;
+        row0 = gr[0]; n = gr[1]; point0 = gr[2]; c0 = gr[3]; c1 = gr[4];
+    }
+    bool valid = n > 0 && first >= 0 && first < n && point0 >= 0 && (long long)point0 + n <= N;
+    if (!(c0 >= 0 && c0 <= c1 && c1 <= C && c1 - c0 <= TP_ENTRIES && row0 >= 0 && (long long)row0 + (long long)(c1 - c0) * n <= Q)) c1 = c0 = 0;
+    if (!valid) { c0 = c1 = 0; n = 0; }
+    const int i = first + lane;
+    const bool have = valid && i < n;
+    const int in_tile = valid ? (n - first < TP_P ? n - first : TP_P) : 0;
+    const float nan = __uint_as_float(0x7fc00000u), inf = __uint_as_float(0x7f800000u);
+    int buf = 0;
+    for (int tc = t0; tc < t1; tc += TP_F, buf ^= 1) {
+        unsigned long long best[TP_FW];
+        float bx[TP_FW], by[TP_FW], bo[TP_FW], bs[TP_FW];
+#pragma unroll
+        for (int u = 0; u < TP_FW; ++u) { best[u] = TL_NONE; bx[u] = nan; by[u] = nan; bo[u] = 1.f; bs[u] = inf; }
+        for (int k = c0; k < c1; ++k) {
+            // wave-uniform: the candidate's row, rank and its columns' frames
+            const int row = row_of[k];
+            if (row < 0 || row >= R) continue;            // (a table that is not what it should be reads nothing)
+            const unsigned long long rank = (unsigned long long)(rank_of[k] & 0xff);
+            const long long tb = (long long)row * T;
+            const uint2 *frame[TP_FW];
+            const float *lh[TP_FW];
+            bool ok[TP_FW], any = false;
+#pragma unroll
+            for (int u = 0; u < TP_FW; ++u) {
+                const int t = tc + wave + 4 * u;
+                frame[u] = nullptr; lh[u] = nullptr;
+                if (t < t1) { frame[u] = frames[tb + t]; lh[u] = lohis[tb + t]; }
+                ok[u] = frame[u] != nullptr && lh[u] != nullptr;
+                any = any || ok[u];
+            }
+            if (!any) continue;
+            // per lane: did this candidate find the point, and where on its template
+            const long long at = (long long)row0 + (long long)(k - c0) * n + i;
+            int cell = -1;
+            if (have) cell = cells[at];
+            const bool found = cell >= 0;
+            float4 src = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (found) src = located[at];
+            const TsSampler smp(src.x, src.y, sx, sy, H, W);     // ts_query_kernel's sampler at the candidate's template point
+            uint2 q[TP_FW][4];
+            float l[TP_FW][8];
+#pragma unroll
+            for (int u = 0; u < TP_FW; ++u) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) q[u][j] = make_uint2(0u, 0u);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) l[u][j] = 0.f;
+                if (ok[u]) {
+                    if (found) smp.load(frame[u], q[u]);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) l[u][j] = lh[u][j];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < TP_FW; ++u) {
+                const float4 r = ts_chain_behind(src, smp.mix(Dec4(l[u]), q[u]), 0.f, 0.f);
+                const float sg = r.w;
+                const unsigned field = sg != sg ? 0x7fffffffu : (sg > 0.f ? __float_as_uint(sg) : 0u);
+                const unsigned long long key = ((unsigned long long)(r.z <= thr ? 0u : 1u) << 39) | ((unsigned long long)field << 8) | rank;
+                if (ok[u] && found && key < best[u]) { best[u] = key; bx[u] = r.x; by[u] = r.y; bo[u] = r.z; bs[u] = sg; }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < TP_FW; ++u) {
+            tile[buf][lane][wave + 4 * u] = make_float4(bx[u], by[u], bo[u], bs[u]);
+            etile[buf][lane][wave + 4 * u] = best[u] == TL_NONE ? -1 : (int)(best[u] & 0xffull);
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < TP_P * TP_F; e += 256) {
+            const int p = e / TP_F, k = e % TP_F;
+            const int t = tc + k;
+            if (p < in_tile && t < t1) {
+                const int dst = order[(long long)point0 + first + p];
+                if (dst >= 0 && dst < N) {
+                    table[(long long)dst * T + t] = tile[buf][p][k];
+                    entry[(long long)dst * T + t] = etile[buf][p][k];
+                }
+            }
+        }
+    }
+}
+
 static int ts_blocks(long long n) {
     const long long b = (n + (long long)TS_T * TS_PX - 1) / ((long long)TS_T * TS_PX);
     return (int)(b < 1 ? 1 : (b > TS_B_MAX ? TS_B_MAX : b));
@@ -1031,4 +1155,50 @@ extern "C" int mftx_trackstore_flow_from_best(const float *tables, const int *ce
                        reinterpret_cast<const float4 *>(tables), cells, rank_of, row_of, reinterpret_cast<const uint2 *const *>(frames), lohis, E,
                        R, T, cols, H, W, sx, sy, occlusion_threshold, flow, occl, sigma, entry);
     return check_launch("trackstore_flow_from_best");
+}
+
+extern "C" int mftx_trackstore_tracks_from_best(const float *located, const int *cells, const int *tiles, const int *groups,
+                                                const int *rank_of, const int *row_of, const int *order,
+                                                const uint16_t *const *frames, const float *const *lohis, int n_tiles, int G, int C,
+                                                int max_candidates, int Q, int N, int R, int T, int H, int W, float occlusion_threshold,
+                                                int columns_per_block, float *table, int *entry, void *stream) {
+    if (N < 0 || T < 0 || n_tiles < 0 || G < 0 || C < 0 || Q < 0 || max_candidates < 0)
+        return fail(MFTX_E_ARG, "trackstore_tracks_from_best: need N, T, n_tiles, G, C, Q, max_candidates >= 0");
+    if (max_candidates > TP_ENTRIES)
+        return fail(MFTX_E_ARG, "trackstore_tracks_from_best: %d candidates in a group: more than %d", max_candidates, TP_ENTRIES);
+    if (H < 2 || W < 2) return fail(MFTX_E_ARG, "trackstore_tracks_from_best: H and W must be >= 2");
+    if (columns_per_block < 0) return fail(MFTX_E_ARG, "trackstore_tracks_from_best: columns_per_block must be >= 0 (0: the default)");
+    if ((long long)H * W > 0x7fffffffLL) return fail(MFTX_E_ARG, "trackstore_tracks_from_best: more than 2^31 - 1 pixels");
+    if (N == 0 || T == 0) return 0;
+    if (n_tiles < 1 || G < 1 || G > n_tiles || n_tiles > N)
+        return fail(MFTX_E_ARG, "trackstore_tracks_from_best: need 1 <= G <= n_tiles <= N groups and tiles of the N points");
+    if (max_candidates > C || (C > 0 && (R < 1 || Q < 1)))
+        return fail(MFTX_E_ARG, "trackstore_tracks_from_best: with candidates need R >= 1, Q >= 1 and max_candidates <= C");
+    const struct { const void *p; const char *name; bool always; } ptrs[] = {
+        {located, "located", false}, {cells, "cells", false}, {rank_of, "rank_of", false}, {row_of, "row_of", false}, {frames, "frames", false},
+        {lohis, "lohis", false}, {tiles, "tiles", true}, {groups, "groups", true}, {order, "order", true}, {table, "table", true},
+        {entry, "entry", true}};
+    for (const auto &a : ptrs)           // (without candidates nothing but the tiles and the results is touched)
+        if (!a.p && (a.always || C > 0)) return fail(MFTX_E_ARG, "trackstore_tracks_from_best: null pointer: %s", a.name);
+    const int cols = columns_per_block ? columns_per_block : TP_COLS;
+    const long long col_blocks = ((long long)T + cols - 1) / cols;
+    if (col_blocks > 65535)
+        return fail(MFTX_E_ARG, "trackstore_tracks_from_best: T = %d in blocks of %d columns: more than 65535 column blocks", T, cols);
+    if (!aligned16(located)) return fail(MFTX_E_ALIGN, "trackstore_tracks_from_best: located must be 16-byte aligned");
+    if (!aligned16(table)) return fail(MFTX_E_ALIGN, "trackstore_tracks_from_best: table must be 16-byte aligned");
+    if (!aligned_to(frames, 8) || !aligned_to(lohis, 8))
+        return fail(MFTX_E_ALIGN, "trackstore_tracks_from_best: the pointer tables frames and lohis must be 8-byte aligned");
+    for (const auto &a : ptrs)
+        if (!aligned_to(a.p, 4)) return fail(MFTX_E_ALIGN, "trackstore_tracks_from_best: %s must be 4-byte aligned", a.name);
+    float sx, sy;
+    grid_scales(H, W, sx, sy);
+    hipStream_t s = (hipStream_t)stream;
+    // per point, candidate and chunk of TP_F columns: a row and a cell in each wave; per point, column and candidate (at most): 4 taps
+    // of 8 B; per point and column: 20 B of results
+    ProfScope prof(PC_CHAIN, s, 20.0 * 4.0 * (double)Q * (double)((T + TP_F - 1) / TP_F) + 32.0 * (double)Q * (double)T + 20.0 * (double)N * (double)T);
+    hipLaunchKernelGGL(ts_tracks_best_kernel, dim3((unsigned)n_tiles, (unsigned)col_blocks), dim3(256), 0, s,
+                       reinterpret_cast<const float4 *>(located), cells, tiles, groups, rank_of, row_of, order,
+                       reinterpret_cast<const uint2 *const *>(frames), lohis, G, C, Q, N, R, T, cols, H, W, sx, sy, occlusion_threshold,
+                       reinterpret_cast<float4 *>(table), entry);
+    return check_launch("trackstore_tracks_from_best");
 }

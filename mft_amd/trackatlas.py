@@ -15,6 +15,8 @@ frame -- and a template in the middle of a video has its forward and backward ha
     result, found, template = atlas.result_from(57, 80)               # ... one column as a FlowOUTrackingResult
     flow, occl, sigma, entry, template = atlas.best_results_from(57)  # ... the template chosen per pixel AND column: [T, H, W] x 2
     result, found, template = atlas.best_result_from(57, 12)          # ... one column of that
+    table, entry, template = atlas.best_query_from(points, 57)        # device [N, T, 4], [N, T] x 2: that choice for POINTS; frame: one id or N ids
+    coords, occl, found, template = atlas.best_tracks_from(points, 57)  # numpy (N, T, 2), (N, T) x 3: ONE download
     atlas.covered(template_frame)                                    # list of bool: the frames some entry of that template holds
 
 The definition (and the ``device="cpu"`` path; there is no new arithmetic): for a query on frame ``f`` every entry whose store holds
@@ -37,6 +39,12 @@ cover is fill even where another template sees the pixel and holds the column --
 frame that is every pixel.  ``best_results_from`` makes every entry that holds the source frame a candidate and lets the smallest
 (occluded, chained sigma, rank) win each (pixel, column): per-entry inverses, then ONE ``mftx_trackstore_flow_from_best`` launch
 (mft_amd/atlas_ops.py).
+
+``tracks_from`` has ``results_from``'s rule for sparse points, and ``best_query_from`` / ``best_tracks_from`` are its
+``best_results_from``: per (point, column) the same key among all entries that hold the point's frame, each candidate with its OWN
+``store.locate`` row, the position chained in the place of the flow.  The points may be given on several frames in one call.  On the
+device: the ``mftx_trackstore_locate`` call of ``locate`` with its rows kept un-reduced, then ONE
+``mftx_trackstore_tracks_from_best`` launch (mft_amd/atlas_ops.py) over tiles of at most 64 points of one source frame.
 """
 from __future__ import annotations
 
@@ -480,6 +488,168 @@ class TrackAtlas:
         tmpl_of = self._upload(np.asarray([f for f, _ in self.entries], dtype=np.int32))
         template = torch.where(entry >= 0, tmpl_of[entry.clamp(min=0).to(torch.int64)], torch.full((), -1, dtype=torch.int32, device=self.device))
         return out[0], out[1], out[2], entry, template
+
+    # ------------------------------------------------------------------ ... and per POINT and destination frame
+    def _point_groups(self, frame, N, name):
+        """``frame`` as for ``locate`` -> (groups: per distinct source frame, ascending, (frame, the rows of the points given on it, or
+        None for all of them); holders: per group the ranks of its candidates).  ``KeyError`` for a frame that no entry holds."""
+        ids, lead = _frame_ids(frame, name, N)
+        if lead:
+            groups = [(int(f), np.flatnonzero(ids == f)) for f in np.unique(ids)]
+            if len(groups) == 1:
+                groups = [(groups[0][0], None)]                              # (N ids of one frame: the points as they are)
+        else:
+            groups = [(int(ids[0]), None)]
+        return groups, [self._holders(f) for f, _ in groups]
+
+    def _locate_candidates(self, xy, groups, holders, thr):
+        """Step A of ``best_query_from``: every candidate's OWN ``store.locate`` of its group's points, un-reduced -> (rows [Q, 4],
+        cells [Q]): group after group and, within a group of n points, candidate after candidate (row = the group's first +
+        k * n + i).  On the device ONE ``ops.trackstore_locate_frames`` call, the call ``locate`` makes."""
+        N = int(xy.shape[0])
+        sizes = [N if pts is None else len(pts) for _, pts in groups]
+        Q = sum(n * len(ranks) for n, ranks in zip(sizes, holders))
+        tq = torch.empty((Q, 4), dtype=torch.float32, device=self.device)
+        cq = torch.empty((Q,), dtype=torch.int32, device=self.device)
+        if Q == 0:
+            return tq, cq
+        if self.native:
+            from . import ops
+            views, which, index = [], [], []
+            for (f, pts), ranks, n in zip(groups, holders, sizes):
+                for r in ranks:
+                    which.append(np.full(n, len(views), np.int64))
+                    views.append(self._frame_views(r, f))
+                    index.append(np.arange(N) if pts is None else pts)
+            if len(groups) == 1 and groups[0][1] is None:
+                xq = xy.repeat(len(views), 1)
+            else:
+                xq = xy.index_select(0, self._upload(np.concatenate(index).astype(np.int64)))
+            ops.trackstore_locate_frames(views, np.concatenate(which), xq, tq, cq, thr)
+        else:
+            q0 = 0
+            for (f, pts), ranks, n in zip(groups, holders, sizes):
+                x = xy if pts is None else xy[torch.from_numpy(pts)]
+                for r in ranks:
+                    self.entries[r][1].locate(x, f, thr, out=(tq[q0:q0 + n], cq[q0:q0 + n]))
+                    q0 += n
+        return tq, cq
+
+    def _compose_best_points(self, tq, cq, groups, holders, cols, thr, N):
+        """The definition of ``best_query_from`` in torch, on the atlas's device: tq [Q, 4] and cq [Q] of ``_locate_candidates``.  Frame
+        group after frame group and candidate after candidate: its located template points followed by ``query`` on its template,
+        chained behind ITS located row by ``chain_behind_inverse`` with a grid of zeros (the position in the place of the flow),
+        keyed as ``_compose_best`` keys, and kept where the key is smaller than the best so far -> (table [N, T, 4], entry [N, T]
+        int32)."""
+        T, dev = len(cols), self.device
+        nan, one, inf, zero = (torch.full((), v, dtype=torch.float32, device=dev) for v in (float("nan"), 1.0, float("inf"), 0.0))
+        none = torch.full((), _NOT_FOUND, dtype=torch.int64, device=dev)
+        limit = torch.tensor(thr, dtype=torch.float32, device=dev)
+        table = torch.empty((N, T, 4), dtype=torch.float32, device=dev)
+        entry = torch.empty((N, T), dtype=torch.int32, device=dev)
+        q0 = 0
+        for (_, pts), ranks in zip(groups, holders):
+            n = N if pts is None else len(pts)
+            pos, occl, sigma = nan.expand(T, 2, n).clone(), one.expand(T, n).clone(), inf.expand(T, n).clone()
+            best = torch.full((T, n), _NOT_FOUND, dtype=torch.int64, device=dev)
+            origin = torch.zeros((n, 2), dtype=torch.float32, device=dev)
+            for r in ranks:
+                tb, found = tq[q0:q0 + n], cq[q0:q0 + n] >= 0
+                q0 += n
+                s = self.entries[r][0]
+                cov = np.asarray(self.covered(s, cols), dtype=bool)
+                if not (T and n and cov.any()):
+                    continue
+                ok = found[:, None] & self._upload(cov)[None, :]
+                q = self.query(s, torch.where(found[:, None], tb[:, 0:2], zero), cols)
+                p, o, sg = chain_behind_inverse(tb, q, origin, ok)                               # [T, 2, n], [T, n], [T, n]
+                field = torch.where(sg > 0, sg, zero).contiguous().view(torch.int32).to(torch.int64)
+                field = torch.where(torch.isnan(sg), torch.full((), 0x7fffffff, dtype=torch.int64, device=dev), field)
+                key = ((~(o <= limit)).to(torch.int64) << 39) | (field << 8) | int(r)
+                key = torch.where(ok.t(), key, none)
+                better = key < best
+                best = torch.where(better, key, best)
+                pos, occl, sigma = torch.where(better[:, None, :], p, pos), torch.where(better, o, occl), torch.where(better, sg, sigma)
+            rows = torch.cat([pos, occl[:, None], sigma[:, None]], dim=1).permute(2, 0, 1)      # [n, T, 4]
+            won = torch.where(best != none, (best & 0xff).to(torch.int32), torch.full((), -1, dtype=torch.int32, device=dev)).t()
+            if pts is None:
+                table.copy_(rows)
+                entry.copy_(won)
+            else:
+                at = self._upload(pts.astype(np.int64))
+                table.index_copy_(0, at, rows)
+                entry.index_copy_(0, at, won)
+        return table, entry
+
+    def _points_tables(self, groups, holders, cols, N):
+        """The host tables of ``atlas_ops.trackstore_tracks_from_best`` -> (group sizes, candidates per group, rank_of, row_of, order,
+        frame_ptrs [R, T], lohi_ptrs [R, T])."""
+        row_of, frame_ptrs, lohi_ptrs = self._flow_tables(cols)
+        sizes = [N if pts is None else len(pts) for _, pts in groups]
+        order = np.concatenate([np.arange(N) if pts is None else pts for _, pts in groups]) if groups else np.zeros(0, np.int64)
+        ranks = [r for rs in holders for r in rs]
+        return sizes, [len(rs) for rs in holders], ranks, [row_of[r] for r in ranks], order, frame_ptrs, lohi_ptrs
+
+    def best_query_from(self, points, frame, frames=None, occlusion_threshold=0.5, out=None):
+        """points (N, 2) xy given ON video frame(s) ``frame`` -- one frame id, or a host sequence of N ids, exactly as for ``locate`` --
+        followed over ``frames`` (default: ``atlas.frames``) with the template chosen per point AND column -> (table [N, T, 4]
+        float32 = (x, y, occlusion, sigma), entry [N, T] int32, template [N, T] int32) on the atlas's device: the sparse sibling of
+        ``best_results_from``.  ``tracks_from`` follows each point on the ONE entry that wins ``locate`` and fills the columns that
+        entry's template does not cover.  Here, for point n given on frame f, the candidates are ALL entries that hold f, in
+        ascending rank; candidate k takes the point back by its OWN ``store.locate(point, f, thr)`` -- (Px, Py, o_src, s_src) and a
+        cell -- follows (Px, Py) by ``query`` on its template -- (qx, qy, o_dst, s_dst) per column -- and chains by
+        ``chain_behind_inverse`` with the position in the place of the flow: (qx, qy, max(o_src, o_dst) with a NaN of either kept,
+        sqrt(s_src^2 + s_dst^2) correctly rounded).  It has an answer for (n, column t) iff its cell is >= 0 and its template covers
+        t, and among those the smallest key of ``best_results_from`` wins, unchanged.  ``entry`` is the winner's rank and
+        ``template`` its template frame; where no candidate has an answer the row is NaN, NaN, 1, +inf, -1, -1.  The occlusion is
+        the CHAINED maximum, where ``tracks_from`` returns the destination's alone.  ``out``: a (table, entry) pair of contiguous
+        tensors of those shapes and dtypes on the atlas's device; ``template`` is allocated by the call.  ``KeyError`` for a frame
+        that no entry holds, ``ValueError`` for an ``out`` that does not fit or malformed ``points`` / ``frame``, all before any
+        work.  N = 0 or T = 0 returns empty results and launches nothing.  On the device: ONE ``mftx_trackstore_locate`` call (the
+        points repeated per candidate, its rows kept un-reduced), one table upload and ONE ``mftx_trackstore_tracks_from_best``
+        launch (mft_amd/atlas_ops.py); with ``points`` a device tensor no host synchronisation."""
+        xy = _as_points(points, self.device, "TrackAtlas.best_query_from")
+        N = int(xy.shape[0])
+        groups, holders = self._point_groups(frame, N, "TrackAtlas.best_query_from")          # ValueError, KeyError before any work
+        cols = list(self.frames) if frames is None else [int(f) for f in frames]
+        T = len(cols)
+        if out is not None:
+            out = tuple(out)
+            want = (((N, T, 4), torch.float32), ((N, T), torch.int32))
+            if len(out) != 2 or any(not isinstance(o, torch.Tensor) or tuple(o.shape) != s or o.dtype != d or
+                                    not _same_device(o.device, self.device) or not o.is_contiguous() for o, (s, d) in zip(out, want)):
+                raise ValueError(f"TrackAtlas.best_query_from: out must be contiguous (float32 [{N}, {T}, 4], int32 [{N}, {T}]) tensors "
+                                 f"on {self.device}")
+        else:
+            out = (torch.empty((N, T, 4), dtype=torch.float32, device=self.device),
+                   torch.empty((N, T), dtype=torch.int32, device=self.device))
+        table, entry = out
+        if N == 0 or T == 0:
+            return table, entry, torch.empty((N, T), dtype=torch.int32, device=self.device)
+        thr = float(occlusion_threshold)
+        tq, cq = self._locate_candidates(xy, groups, holders, thr)
+        if self.native:
+            from . import atlas_ops
+            atlas_ops.trackstore_tracks_from_best(tq, cq, *self._points_tables(groups, holders, cols, N), (self.H, self.W), table, entry, thr)
+        else:
+            t, e = self._compose_best_points(tq, cq, groups, holders, cols, thr, N)
+            table.copy_(t)
+            entry.copy_(e)
+        tmpl_of = self._upload(np.asarray([f for f, _ in self.entries], dtype=np.int32))
+        template = torch.where(entry >= 0, tmpl_of[entry.clamp(min=0).to(torch.int64)], torch.full((), -1, dtype=torch.int32, device=self.device))
+        return table, entry, template
+
+    def best_tracks_from(self, points, frame, frames=None, occlusion_threshold=0.5):
+        """``tracks_from`` with the template chosen per point AND column: ``best_query_from`` brought to the host -> numpy (coords
+        [N, T, 2], occlusion [N, T], found [N, T] bool, template [N, T] int64).  Where no candidate answers a point-column:
+        NaN coordinates, occlusion 1, found False, template -1.  With a single holder of the source frame the coordinates are
+        ``tracks_from``'s bit for bit; the occlusion is the chained maximum max(o_src, o_dst), where ``tracks_from`` returns the
+        destination's o_dst alone.  ONE download; it synchronises."""
+        table, _, template = self.best_query_from(points, frame, frames, occlusion_threshold)
+        N, T = int(table.shape[0]), int(table.shape[1])
+        both = torch.cat([table.reshape(N, T * 4), template.to(torch.float32)], dim=1).cpu().numpy()
+        tracks, template = both[:, :T * 4].reshape(N, T, 4), both[:, T * 4:].astype(np.int64)
+        return tracks[:, :, 0:2].copy(), tracks[:, :, 2].copy(), template >= 0, template
 
     def best_result_from(self, src, dst, occlusion_threshold=0.5):
         """-> (``FlowOUTrackingResult`` of the flow from video frame ``src`` to video frame ``dst``, found [H, W] bool, template
