@@ -143,6 +143,13 @@ __device__ __forceinline__ void split_pair(float x0, float x1, float k2048, unsi
         : "v"(x0), "v"(x1), "s"(k2048));
 }
 
+// One dword of a packed weight fragment: two consecutive k values of an MFMA operand row, their high halves (part 0) or their
+// low halves (part 1) -- every pack kernel's word (split_halves: common.h, included before this header by every kernel file)
+__device__ __forceinline__ unsigned frag_word(float v0, float v1, int part) {
+    const unsigned a = split_halves(v0), b = split_halves(v1);
+    return part ? ((a >> 16) | (b & 0xffff0000u)) : ((a & 0xffffu) | (b << 16));
+}
+
 // Gate non-linearities of the GRU epilogues on the hardware exponential (v_exp_f32, ~1 ulp) and
 // reciprocal: 16 values per lane and tile, where libm's expf / tanhf cost ~7 % of the q-gate kernel.
 // Absolute error < 2e-7 on outputs in (-1, 1) -- four orders below the parity tolerance; the same

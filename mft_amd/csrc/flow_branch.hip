@@ -345,10 +345,7 @@ __global__ void pack_flow_branch_kernel(const float *__restrict__ w98, const flo
     }
     unsigned w[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const unsigned a = split_halves(v[2 * e]), b = split_halves(v[2 * e + 1]);
-        w[e] = part ? ((a >> 16) | (b & 0xffff0000u)) : ((a & 0xffffu) | (b << 16));
-    }
+    for (int e = 0; e < 4; ++e) w[e] = frag_word(v[2 * e], v[2 * e + 1], part);
     out[idx] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 

@@ -22,6 +22,19 @@
 // Results do not depend on the batch or on a cell's place in its tile (one fixed sequence of products and sums per
 // output).  They differ from conv_gemm.hip's in the order of the K sum (tap-major here as there, but the cross terms
 // go to their accumulator in another order for N = 128): fp32 rounding.
+//
+// Four kernels live here -- tile_conv_kernel (one layer), gru_half_kernel (a SepConvGRU pass: two GEMMs over one tile),
+// ou_head_kernel (712 channels in five passes + projection) and tile_conv2p_kernel (256 channels in two passes) -- and they are
+// made of the same pieces, each defined once above them ("One tile body"):
+//   TC_TILE            workgroup -> tile column and row, image and the image's first cell (a macro: see there)
+//   TC_LOAD_TILE       the halo tile -> LDS in rounds of B pieces per thread; the caller says where a piece comes from (a macro: see there)
+//   TC_SET_ABASE       the lane's A-fragment addresses (a macro: see there)          tc_zero    the accumulators
+//   tc_kloop           the K loop                                                    tc_sum4    acc + accx / 2048, four channels
+//   tc_park            a wave's sums -> LDS                                          tc_project the projection epilogue (18 / 27 out)
+//   tc_store_split8 / tc_store_halves8   8 channels of a split-form row             tc_gru_blend8   h <- (1 - z) h + z tanh(.)
+//   tc_tile_h, bad_split_row, tc_launch_tiles   host side: tile shape by filter and cells, row check, the launch itself
+// and frag_word (device_prims.h), the word of a packed weight fragment, for the pack kernels.  tests/test_gpu_tile_family_bits.py
+// pins the family's output bits across commits.
 #include "common.h"
 #include "profile.h"
 #include "device_prims.h"
@@ -71,85 +84,86 @@ struct TcGeom {
     static constexpr int A_BYTES = HCELLS * CELLB, RED_BYTES = KS * CELLS * RED_ROW * 4;
     static constexpr int LDS = A_BYTES > RED_BYTES ? A_BYTES : RED_BYTES;
     static constexpr int PROJ_ROW = 20, PROJ_BYTES = 2 * CELLS * PROJ_ROW * 4;        // TC_RELU_PROJ: two K halves of [cell][18 (+ 2)] behind the parked sums
+    static constexpr int TILE_W = TW, HALO_Y = KH / 2, HALO_X = KW / 2;         // (for the shared pieces below)
     static_assert((CELLS == 128 || CELLS == 64 || CELLS == 32) && (N == 128 || N == 256) && (CIN == 128 || CIN == 256 || CIN == 144), "tile_conv: shapes");
     static_assert(LDS <= 160 * 1024, "tile_conv: the input tile must fit the CU's LDS");
 };
 
-template <int TH, int TW, int KH, int KW, int CIN, int N, int EPI>
-__global__ __launch_bounds__(512, 2) void tile_conv_kernel(TileConvArgs p) {
-    using G = TcGeom<TH, TW, KH, KW, CIN, N>;
-    extern __shared__ __attribute__((aligned(16))) unsigned char tc_lds[];
-    unsigned char *lds = tc_lds;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tile = (int)blockIdx.x;
-    const int tx_ = tile % p.tiles_x, ty_ = (tile / p.tiles_x) % p.tiles_y, img = tile / (p.tiles_x * p.tiles_y);
-    const int x0 = tx_ * TW, y0 = ty_ * TH;
-    const long long img_base = (long long)img * p.h * p.w;
-    const int nt = wv % G::NT, ks = wv / G::NT;
-    const uint4 *__restrict__ w2 = reinterpret_cast<const uint4 *>(p.wf) + (long long)((nt * G::KS + ks) * G::STEPS) * 128 + lane;
+// ---- the pieces the four kernels are made of, each defined ONCE ("One tile body") ---------------------------------
+// That a tile's result does not depend on which kernel computed it rests on these being the same code, not equal copies.
 
-#ifdef MFTX_LF_TRACE
-    int tcount = 0;
-#endif
-    TC_T(1);
-    TC_CLK(0);
-    // weight fragments of the first steps: in flight while the input tile loads
-    constexpr int PF = 3;
-    uint4 bq[PF][2];
-#pragma unroll
-    for (int s = 0; s < PF; ++s) { bq[s][0] = w2[s * 128]; bq[s][1] = w2[s * 128 + 64]; }
+// workgroup -> its tile: declares tx_, ty_ (the tile's column and row), img and img_base (the image and its first cell in the
+// batch) from the kernel's argument struct.  One macro text expanded in place: as a function returning a struct it changed
+// gru_half_kernel's code more than any other piece ("One tile body").  A tile's first output cell is
+// (tx_ * TW, ty_ * TH); gru_half_kernel puts its own R-cell origin in its place.
+#define TC_TILE(p)                                                                                                             \
+    const int tile_ = (int)blockIdx.x;                                                                                         \
+    const int tx_ = tile_ % (p).tiles_x, ty_ = (tile_ / (p).tiles_x) % (p).tiles_y, img = tile_ / ((p).tiles_x * (p).tiles_y); \
+    const long long img_base = (long long)img * (p).h * (p).w
 
-    // ---- the input tile (halo included) -> LDS, 16-byte pieces, zeros outside the image
-    {
-        constexpr int PPC = CIN / 4;                         // pieces per cell
-        constexpr int TOTAL = G::HCELLS * PPC, ROUNDS = (TOTAL + 511) / 512, B = 6;
-#pragma unroll 1
-        for (int r0 = 0; r0 < ROUNDS; r0 += B) {
-            uint4 v[B];
-#pragma unroll
-            for (int k = 0; k < B; ++k) {
-                const int q = (r0 + k) * 512 + tid;
-                v[k] = make_uint4(0u, 0u, 0u, 0u);
-                if (r0 + k < ROUNDS && q < TOTAL) {
-                    const int c = q / PPC, pc = q - c * PPC;
-                    const int cy = c / G::HWD, cx = c - cy * G::HWD;
-                    const int yy = y0 - KH / 2 + cy, xx = x0 - KW / 2 + cx;
-                    if (yy >= 0 && yy < p.h && xx >= 0 && xx < p.w) {
-                        const long long cell = img_base + (long long)yy * p.w + xx;
-                        const float *src = (CIN == 256 && pc >= 32) ? p.a1 + cell * p.lda1 + (pc - 32) * 4 : p.a0 + cell * p.lda0 + pc * 4;
-                        v[k] = *reinterpret_cast<const uint4 *>(src);
-                    }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < B; ++k) {
-                const int q = (r0 + k) * 512 + tid;
-                if (r0 + k < ROUNDS && q < TOTAL) {
-                    const int c = q / PPC, pc = q - c * PPC;
-                    *reinterpret_cast<uint4 *>(lds + c * G::CELLB + pc * 16) = v[k];
-                }
-            }
-        }
-    }
-    TC_T(2);
-    lds_barrier();
-    TC_T(3);
+__device__ __forceinline__ float tc_k2048() { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(0x45000000)); }
 
-    // ---- the K loop
-    f32x16 acc[G::RT], accx[G::RT];
+// The input tile (halo included) -> LDS: rounds of B 16-byte pieces per thread, PPC pieces per cell, all of a round's loads in
+// flight before its LDS stores; zeros outside the image, else PIECE: an expression in the names `cell` (the cell's index in the
+// batch) and `pc` (the piece's index in the cell) that loads the piece with tc_piece -- or gives zeros where the caller has none.
+// (x0, y0): the tile's first output cell; the halo tile starts G::HALO_Y rows and G::HALO_X columns before it.
+// One macro text expanded in place, not a function taking a callable: as a function some instantiations lost the address space
+// of the source (flat loads) and the 5 x 1 kernels at 32 / 64 cells measured 1.5-2.4 % slower ("One tile body").
+__device__ __forceinline__ uint4 tc_piece(const float *src) { return *reinterpret_cast<const uint4 *>(src); }
+#define TC_LOAD_TILE(G, PPC, B, lds, tid, x0, y0, h, w, img_base, PIECE)                                                        \
+    do {                                                                                                                       \
+        constexpr int PPC_ = (PPC), B_ = (B), TOTAL_ = G::HCELLS * PPC_, ROUNDS_ = (TOTAL_ + 511) / 512;                        \
+        _Pragma("unroll 1") for (int r0_ = 0; r0_ < ROUNDS_; r0_ += B_) {                                                      \
+            uint4 v_[B_];                                                                                                      \
+            _Pragma("unroll") for (int k_ = 0; k_ < B_; ++k_) {                                                                \
+                const int q_ = (r0_ + k_) * 512 + (tid);                                                                       \
+                v_[k_] = make_uint4(0u, 0u, 0u, 0u);                                                                           \
+                if (r0_ + k_ < ROUNDS_ && q_ < TOTAL_) {                                                                       \
+                    const int c_ = q_ / PPC_, pc = q_ - c_ * PPC_;                                                             \
+                    const int cy_ = c_ / G::HWD, cx_ = c_ - cy_ * G::HWD;                                                      \
+                    const int yy_ = (y0) - G::HALO_Y + cy_, xx_ = (x0) - G::HALO_X + cx_;                                      \
+                    if (yy_ >= 0 && yy_ < (h) && xx_ >= 0 && xx_ < (w)) {                                                      \
+                        const long long cell = (img_base) + (long long)yy_ * (w) + xx_;                                        \
+                        v_[k_] = (PIECE);                                                                                      \
+                    }                                                                                                          \
+                }                                                                                                              \
+            }                                                                                                                  \
+            _Pragma("unroll") for (int k_ = 0; k_ < B_; ++k_) {                                                                \
+                const int q_ = (r0_ + k_) * 512 + (tid);                                                                       \
+                if (r0_ + k_ < ROUNDS_ && q_ < TOTAL_) {                                                                       \
+                    const int c_ = q_ / PPC_, pc_ = q_ - c_ * PPC_;                                                            \
+                    *reinterpret_cast<uint4 *>((lds) + c_ * G::CELLB + pc_ * 16) = v_[k_];                                     \
+                }                                                                                                              \
+            }                                                                                                                  \
+        }                                                                                                                      \
+    } while (0)
+
+// a lane's A-fragment addresses, one per row tile: cell 32 i + (lane & 31) of the tile, k half lane >> 5, plus the wave's K-split
+// offset in bytes.  One macro text expanded in place, not a function: as a function the compiler keeps ONE base register for
+// all row tiles and pays a v_add_u32 for every ds_read whose offset no longer fits 16 bits ("One tile body").
+#define TC_SET_ABASE(G, abase, lds, lane, ks_off)                                                                              \
+    do {                                                                                                                       \
+        const int r_ = (lane) & 31;                                                                                            \
+        _Pragma("unroll") for (int i_ = 0; i_ < G::RT; ++i_) {                                                                 \
+            const int m_ = 32 * i_ + r_;                                                                                       \
+            (abase)[i_] = (lds) + ((m_ / G::TILE_W) * G::HWD + (m_ % G::TILE_W)) * G::CELLB + ((lane) >> 5) * 32 + (ks_off);   \
+        }                                                                                                                      \
+    } while (0)
+
+template <int RT>
+__device__ __forceinline__ void tc_zero(f32x16 (&acc)[RT], f32x16 (&accx)[RT]) {
 #pragma unroll
-    for (int i = 0; i < G::RT; ++i)
+    for (int i = 0; i < RT; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc[i][r] = 0.f; accx[i][r] = 0.f; }
-    const unsigned char *abase[G::RT];
-    {
-        const int r = lane & 31;
-#pragma unroll
-        for (int i = 0; i < G::RT; ++i) {
-            const int m = 32 * i + r;
-            abase[i] = lds + ((m / TW) * G::HWD + (m % TW)) * G::CELLB + (lane >> 5) * 32 + ks * 64;
-        }
-    }
+}
+
+// The K loop: per 16-wide k group the A fragments of the next step (LDS, compile-time offsets), the weight fragments three steps
+// ahead (global -> registers) and 3 RT MFMAs: main terms to acc, the two cross terms to accx
+template <class G, int KW>
+__device__ __forceinline__ void tc_kloop(const unsigned char *const (&abase)[G::RT], const uint4 *__restrict__ w2, uint4 (&bq)[3][2],
+                                         f32x16 (&acc)[G::RT], f32x16 (&accx)[G::RT]) {
+    constexpr int PF = 3;
     f16x8 ah[2][G::RT], al[2][G::RT];
     auto read_a = [&](int s, int set) {
         const int tap = s / G::GPW, gg = s % G::GPW;
@@ -177,39 +191,60 @@ __global__ __launch_bounds__(512, 2) void tile_conv_kernel(TileConvArgs p) {
         for (int i = 0; i < G::RT; ++i) accx[i] = mfma_f16(bh, al[set][i], accx[i]);
         __builtin_amdgcn_sched_barrier(0);
     }
-    TC_T(4);
-    lds_barrier();           // every wave is done with the input tile: its space takes the sums
-    TC_T(5);
+}
 
-    // ---- sums -> LDS [K split][cell][channel]
+// main + cross / 2048 of a lane's accumulator registers 4 b .. 4 b + 3 (four consecutive channels of one cell).  The expression as
+// written: what the compiler contracts of it is part of the bits.
+__device__ __forceinline__ f32x4 tc_sum4(const f32x16 &acc, const f32x16 &accx, int b) {
     const float inv2048 = 1.f / 2048.f;
-    float *red = reinterpret_cast<float *>(lds);
+    f32x4 v;
 #pragma unroll
-    for (int i = 0; i < G::RT; ++i)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            f32x4 v;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = acc[i][4 * b + e] + accx[i][4 * b + e] * inv2048;
-            *reinterpret_cast<f32x4 *>(red + (ks * G::CELLS + 32 * i + (lane & 31)) * G::RED_ROW + 32 * nt + 8 * b + 4 * (lane >> 5)) = v;
-        }
-    TC_T(6);
-    lds_barrier();
-    TC_T(7);
+    for (int e = 0; e < 4; ++e) v[e] = acc[4 * b + e] + accx[4 * b + e] * inv2048;
+    return v;
+}
 
-    const float k2048 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(0x45000000));
-    if constexpr (EPI == TC_RELU_PROJ) {
-        // The flow head (core/update.py:6-14): delta = conv2(relu(conv1(h))), conv2 a 3 x 3 filter with TWO outputs.  Its 256
-        // input channels are this kernel's output, and by linearity
-        //     delta[c][o] = b2[o] + sum over taps t of T[c + offset(t)][t][o],   T[c'][t][o] = sum_k relu(conv1)[c'][k] W2[o][k][t]:
-        // the 18 numbers T[c'][.][.] need cell c' alone.  So relu(conv1) -- 29 MB per iteration at 7 pairs of 512 x 512 -- is
-        // never stored: the tile's [128 cells x 256] block, parked in LDS, is multiplied here with W2 as a [256 x 18] matrix
-        // (split arithmetic; 192 more MFMAs after the layer's 6912) and only T leaves (2 MB); flow_head_sum_kernel adds the
-        // nine shifted terms.  Wave (row tile mt, K half kh): 8 k groups; the halves meet in LDS, summed in a fixed order.
-        const int mt = wv & 3, kh = wv >> 2;         // (tiles of fewer than 128 cells: the waves of the missing row tiles only keep the barriers)
-        const uint4 *__restrict__ wp = reinterpret_cast<const uint4 *>(p.wproj) + lane;
-        float *tp = reinterpret_cast<float *>(lds + G::RED_BYTES);
-        if (mt < G::RT) {
+// this wave's sums -> LDS: cell m at dst + (row0 + m) * rowf floats, the wave's 32 channels from column col0
+template <int RT>
+__device__ __forceinline__ void tc_park(const f32x16 (&acc)[RT], const f32x16 (&accx)[RT], float *dst, int row0, int rowf, int col0, int lane) {
+#pragma unroll
+    for (int i = 0; i < RT; ++i)
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+            *reinterpret_cast<f32x4 *>(dst + (row0 + 32 * i + (lane & 31)) * rowf + col0 + 8 * b + 4 * (lane >> 5)) = tc_sum4(acc[i], accx[i], b);
+}
+
+// 8 channels c0 .. c0 + 7 (c0 % 8 == 0) of a split-form row
+__device__ __forceinline__ void tc_store_halves8(float *row, int c0, const u32x4 &hi, const u32x4 &lo) {
+    uint4 *dst = reinterpret_cast<uint4 *>(reinterpret_cast<char *>(row) + (c0 >> 3) * 32);
+    dst[0] = __builtin_bit_cast(uint4, hi);
+    dst[1] = __builtin_bit_cast(uint4, lo);
+}
+__device__ __forceinline__ void tc_store_split8(float *row, int c0, const f32x4 &u, const f32x4 &v, float k2048) {
+    u32x4 hi, lo;
+    split8_raw(u, v, k2048, hi, lo);
+    tc_store_halves8(row, c0, hi, lo);
+}
+
+// the GRU's h <- (1 - z) h + z tanh(.) on 8 channels: (u, v) come in as the candidate's pre-activation and leave as the new h
+__device__ __forceinline__ void tc_gru_blend8(f32x4 &u, f32x4 &v, const f32x4 &z0, const f32x4 &z1, const f32x4 &h0, const f32x4 &h1) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { u[e] = gru_blend(z0[e], h0[e], fast_tanh(u[e])); v[e] = gru_blend(z1[e], h1[e], fast_tanh(v[e])); }
+}
+
+// The projection epilogue (TC_RELU_PROJ, ou_head_kernel): a second 3 x 3 layer with NOUT / 9 outputs behind a 256-channel first
+// layer, by linearity
+//     out[c][o] = b2[o] + sum over taps t of T[c + offset(t)][t][o],   T[c'][t][o] = sum_k relu(layer1)[c'][k] W2[o][k][t]:
+// the NOUT numbers T[c'][.][.] need cell c' alone.  So relu(layer1) -- 29 MB per iteration at 7 pairs of 512 x 512 -- is never
+// stored: the tile's [cells x 256] block, parked in LDS at `red`, is multiplied here with W2 as a [256 x NOUT] matrix (split
+// arithmetic; 192 more MFMAs) and only T leaves; a sum kernel adds the nine shifted terms.  Wave (row tile mt, K half kh): 8 k
+// groups; the halves meet in LDS behind the parked sums, [K half][cell][PROJ_ROW], and are summed in a fixed order.
+template <class G, int PROJ_ROW, int NOUT>
+__device__ __forceinline__ void tc_project(unsigned char *lds, const float *red, const float *bias, const void *wproj, float *tout,
+                                           int x0, int y0, long long img_base, int h, int w, int tid, int lane, int wv, float k2048) {
+    const int mt = wv & 3, kh = wv >> 2;         // (tiles of fewer than 128 cells: the waves of the missing row tiles only keep the barriers)
+    const uint4 *__restrict__ wp = reinterpret_cast<const uint4 *>(wproj) + lane;
+    float *tp = reinterpret_cast<float *>(lds + G::RED_BYTES);
+    if (mt < G::RT) {
         f32x16 d, dx;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { d[r] = 0.f; dx[r] = 0.f; }
@@ -218,8 +253,8 @@ __global__ __launch_bounds__(512, 2) void tile_conv_kernel(TileConvArgs p) {
         for (int gg = 0; gg < 8; ++gg) {
             const int g = 8 * kh + gg;
             f32x4 u = *reinterpret_cast<const f32x4 *>(xrow + 16 * g), v = *reinterpret_cast<const f32x4 *>(xrow + 16 * g + 4);
-            u += *reinterpret_cast<const f32x4 *>(p.bias + 16 * g + 8 * (lane >> 5));
-            v += *reinterpret_cast<const f32x4 *>(p.bias + 16 * g + 8 * (lane >> 5) + 4);
+            u += *reinterpret_cast<const f32x4 *>(bias + 16 * g + 8 * (lane >> 5));
+            v += *reinterpret_cast<const f32x4 *>(bias + 16 * g + 8 * (lane >> 5) + 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { u[e] = relu_keep_nan(u[e]); v[e] = relu_keep_nan(v[e]); }
             u32x4 hi, lo;
@@ -233,22 +268,124 @@ __global__ __launch_bounds__(512, 2) void tile_conv_kernel(TileConvArgs p) {
         }
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-            const int j0 = 8 * b + 4 * (lane >> 5);          // this lane's outputs j0 .. j0 + 3 of cell 32 mt + (lane & 31); 18 exist
-            if (j0 < G::PROJ_ROW) {
-                f32x4 v;
+            const int j0 = 8 * b + 4 * (lane >> 5);          // this lane's outputs j0 .. j0 + 3 of cell 32 mt + (lane & 31); NOUT exist
+            if (j0 < PROJ_ROW) *reinterpret_cast<f32x4 *>(tp + (kh * G::CELLS + 32 * mt + (lane & 31)) * PROJ_ROW + j0) = tc_sum4(d, dx, b);
+        }
+    }
+    lds_barrier();
+    for (int idx = tid; idx < G::CELLS * NOUT; idx += 512) {
+        const int m = idx / NOUT, j = idx - m * NOUT;
+        const int yy = y0 + m / G::TILE_W, xx = x0 + m % G::TILE_W;
+        if (yy < h && xx < w)
+            tout[(img_base + (long long)yy * w + xx) * NOUT + j] = tp[m * PROJ_ROW + j] + tp[(G::CELLS + m) * PROJ_ROW + j];
+    }
+}
+
+// ---- cells per tile, and the host side of a launch ---------------------------------------------------------------------------
+// tile shapes by filter and cells per tile: 3 x 3: 8 x 16 / 4 x 16 / 2 x 16; 1 x 5: 4 x 32 / 2 x 32 / 1 x 32; 5 x 1: 32 x 4 / 32 x 2 / 32 x 1
+constexpr int tc_tile_h(int kh, int cells) { return kh == 3 ? cells / 16 : (kh == 1 ? cells / 32 : 32); }
+
+// The kernel takes the time of ONE tile's K loop however few tiles there are (one workgroup per tile, one per CU): it pays
+// only when its tiles come in nearly whole rounds of the chip (>= 5/8 full) -- 7 pairs of 64 x 64 cells are 224 tiles on 256 CUs, at
+// 256 x 256 pixels (56 tiles) the ring-buffered kernel's 64 x 64 tiles are 30 % faster (bench.py, 332 vs 254 frames/s)
+static int tc_num_cus() {
+    static const int cus = [] {
+        int dev = 0, n = 256;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) n = prop.multiProcessorCount;
+        return n;
+    }();
+    return cus;
+}
+static bool tc_fills(long long tiles) {
+    const long long cus = tc_num_cus(), rounds = (tiles + cus - 1) / cus;
+    return tiles * 8 >= rounds * cus * 5;      // >= 5/8: one refinement of 5 / 6 / 7 pairs of 64 x 64 cells is 2 / 8 / 7 % faster with them, of 4 pairs 8 % slower (tools/bench_pairs.py)
+}
+static long long tc_tiles(int P, int h, int w, int kh, int cells) {
+    const int th = tc_tile_h(kh, cells), tw = cells / th;
+    return (long long)P * cdiv(h, th) * cdiv(w, tw);
+}
+bool tile_conv_fills_chip(int P, int h, int w, int kh, int kw) { (void)kw; return tc_fills(tc_tiles(P, h, w, kh, 128)); }
+bool tile_conv_small_tiles_fill(int P, int h, int w) { return tc_tiles(P, h, w, 3, 32) * 2 >= tc_num_cus(); }
+// Cells per tile (round 4): 128 where such tiles fill the chip; else 64, else 32 -- a smaller tile is the same kernel with fewer
+// MFMA row tiles per wave: every output is the same sequence of products and sums, THE SAME BITS, so the choice may follow the
+// batch (one pair per rank of a sharded frame, a ramp-up frame, a 256 x 256 video) without a pair's result depending on it.
+int tile_conv_cells(int P, int h, int w, int kh) {
+    if (tc_fills(tc_tiles(P, h, w, kh, 128))) return 128;
+    if (tc_fills(tc_tiles(P, h, w, kh, 64)) || tc_tiles(P, h, w, kh, 64) >= tc_num_cus()) return 64;
+    return 32;
+}
+
+static bool bad_split_row(const float *p, int ld) { return (reinterpret_cast<uintptr_t>(p) & 31) != 0 || (ld % 8) != 0; }
+
+// One workgroup of 512 threads per tile (a.tiles_x, a.tiles_y set by the caller), lds_bytes of LDS -- reserved once per kernel:
+// KERN is a template argument, so every instantiation has its own flag
+template <auto KERN, class Args>
+static int tc_launch_tiles(const char *name, const Args &a, int lds_bytes, ProfCat cat, double work, hipStream_t s) {
+    const long long tiles = (long long)a.P * a.tiles_x * a.tiles_y;
+    if (tiles > 0x7fffffffLL) return fail(MFTX_E_ARG, "%s: too many tiles", name);
+    static bool attr_set = false;
+    if (!attr_set) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
+            return fail(MFTX_E_STATE, "%s: cannot reserve %d bytes of LDS", name, lds_bytes);
+        attr_set = true;
+    }
+    ProfScope prof(cat, s, work);
+    hipLaunchKernelGGL(KERN, dim3((unsigned)tiles), dim3(512), lds_bytes, s, a);
+    return check_launch(name);
+}
+
+template <int TH, int TW, int KH, int KW, int CIN, int N, int EPI>
+__global__ __launch_bounds__(512, 2) void tile_conv_kernel(TileConvArgs p) {
+    using G = TcGeom<TH, TW, KH, KW, CIN, N>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char tc_lds[];
+    unsigned char *lds = tc_lds;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    TC_TILE(p);
+    const int x0 = tx_ * TW, y0 = ty_ * TH;
+    const int nt = wv % G::NT, ks = wv / G::NT;
+    const uint4 *__restrict__ w2 = reinterpret_cast<const uint4 *>(p.wf) + (long long)((nt * G::KS + ks) * G::STEPS) * 128 + lane;
+
+#ifdef MFTX_LF_TRACE
+    int tcount = 0;
+#endif
+    TC_T(1);
+    TC_CLK(0);
+    // weight fragments of the first steps: in flight while the input tile loads
+    constexpr int PF = 3;
+    uint4 bq[PF][2];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = d[4 * b + e] + dx[4 * b + e] * inv2048;
-                *reinterpret_cast<f32x4 *>(tp + (kh * G::CELLS + 32 * mt + (lane & 31)) * G::PROJ_ROW + j0) = v;
-            }
-        }
-        }
-        lds_barrier();
-        for (int idx = tid; idx < G::CELLS * 18; idx += 512) {
-            const int m = idx / 18, j = idx - m * 18;
-            const int yy = y0 + m / TW, xx = x0 + m % TW;
-            if (yy < p.h && xx < p.w)
-                p.tout[(img_base + (long long)yy * p.w + xx) * 18 + j] = tp[m * G::PROJ_ROW + j] + tp[(G::CELLS + m) * G::PROJ_ROW + j];
-        }
+    for (int s = 0; s < PF; ++s) { bq[s][0] = w2[s * 128]; bq[s][1] = w2[s * 128 + 64]; }
+
+    // ---- the input tile (halo included) -> LDS: segment 0, then (256 channels) segment 1
+    TC_LOAD_TILE(G, CIN / 4, 6, lds, tid, x0, y0, p.h, p.w, img_base,
+                 tc_piece((CIN == 256 && pc >= 32) ? p.a1 + cell * p.lda1 + (pc - 32) * 4 : p.a0 + cell * p.lda0 + pc * 4));
+    TC_T(2);
+    lds_barrier();
+    TC_T(3);
+
+    // ---- the K loop
+    f32x16 acc[G::RT], accx[G::RT];
+    tc_zero(acc, accx);
+    const unsigned char *abase[G::RT];
+    TC_SET_ABASE(G, abase, lds, lane, ks * 64);
+    tc_kloop<G, KW>(abase, w2, bq, acc, accx);
+    TC_T(4);
+    lds_barrier();           // every wave is done with the input tile: its space takes the sums
+    TC_T(5);
+
+    // ---- sums -> LDS [K split][cell][channel]
+    float *red = reinterpret_cast<float *>(lds);
+    tc_park(acc, accx, red, ks * G::CELLS, G::RED_ROW, 32 * nt, lane);
+    TC_T(6);
+    lds_barrier();
+    TC_T(7);
+
+    const float k2048 = tc_k2048();
+    if constexpr (EPI == TC_RELU_PROJ) {
+        // the flow head (core/update.py:6-14): delta = conv2(relu(conv1(h))), conv2 a 3 x 3 filter with TWO outputs: 18 numbers
+        // per cell leave (2 MB), flow_head_sum_kernel adds the nine shifted terms
+        tc_project<G, G::PROJ_ROW, 18>(lds, red, p.bias, p.wproj, p.tout, x0, y0, img_base, p.h, p.w, tid, lane, wv, k2048);
         TC_T(8);
         TC_CLK(1);
         return;
@@ -276,13 +413,6 @@ __global__ __launch_bounds__(512, 2) void tile_conv_kernel(TileConvArgs p) {
             u += *reinterpret_cast<const f32x4 *>(p.addend + cell * p.ld_addend + n0);
             v += *reinterpret_cast<const f32x4 *>(p.addend + cell * p.ld_addend + n0 + 4);
         }
-        auto store_split = [&](float *row, int c0) {        // 8 channels c0 .. c0 + 7 (c0 % 8 == 0) of a split-form row
-            u32x4 hi, lo;
-            split8_raw(u, v, k2048, hi, lo);
-            uint4 *dst = reinterpret_cast<uint4 *>(reinterpret_cast<char *>(row) + (c0 >> 3) * 32);
-            dst[0] = __builtin_bit_cast(uint4, hi);
-            dst[1] = __builtin_bit_cast(uint4, lo);
-        };
         if constexpr (EPI == TC_GRU_ZR) {                   // [z | r] gates; r is folded into r * h (core/update.py:113-115, 119-121)
 #pragma unroll
             for (int e = 0; e < 4; ++e) { u[e] = fast_sigmoid(u[e]); v[e] = fast_sigmoid(v[e]); }
@@ -292,23 +422,22 @@ __global__ __launch_bounds__(512, 2) void tile_conv_kernel(TileConvArgs p) {
             } else {
                 u *= *reinterpret_cast<const f32x4 *>(p.hf + cell * p.ld_hf + n0 - 128);
                 v *= *reinterpret_cast<const f32x4 *>(p.hf + cell * p.ld_hf + n0 - 128 + 4);
-                store_split(p.rh + cell * 128, n0 - 128);
+                tc_store_split8(p.rh + cell * 128, n0 - 128, u, v, k2048);
             }
         } else if constexpr (EPI == TC_GRU_Q) {             // candidate q, h <- (1 - z) h + z q (core/update.py:116-117, 122-123)
             const f32x4 z0 = *reinterpret_cast<const f32x4 *>(p.z + cell * 128 + n0), z1 = *reinterpret_cast<const f32x4 *>(p.z + cell * 128 + n0 + 4);
             float *hrow = p.hf + cell * p.ld_hf + n0;
             const f32x4 h0 = *reinterpret_cast<const f32x4 *>(hrow), h1 = *reinterpret_cast<const f32x4 *>(hrow + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { u[e] = gru_blend(z0[e], h0[e], fast_tanh(u[e])); v[e] = gru_blend(z1[e], h1[e], fast_tanh(v[e])); }
+            tc_gru_blend8(u, v, z0, z1, h0, h1);
             *reinterpret_cast<f32x4 *>(hrow) = u;
             *reinterpret_cast<f32x4 *>(hrow + 4) = v;
-            store_split(p.hx + cell * p.ld_hx, n0);
+            tc_store_split8(p.hx + cell * p.ld_hx, n0, u, v, k2048);
         } else {
             if constexpr (EPI == TC_RELU) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { u[e] = relu_keep_nan(u[e]); v[e] = relu_keep_nan(v[e]); }
             }
-            if (p.out_split) store_split(p.out + cell * p.ldo, n0);
+            if (p.out_split) tc_store_split8(p.out + cell * p.ldo, n0, u, v, k2048);
             else {
                 *reinterpret_cast<f32x4 *>(p.out + cell * p.ldo + n0) = u;
                 *reinterpret_cast<f32x4 *>(p.out + cell * p.ldo + n0 + 4) = v;
@@ -358,39 +487,6 @@ struct GruHalfArgs {
     int P, h, w, tiles_x, tiles_y, step;
 };
 
-template <class G, int KW>
-__device__ __forceinline__ void tc_kloop(const unsigned char *const (&abase)[G::RT], const uint4 *__restrict__ w2, uint4 (&bq)[3][2],
-                                         f32x16 (&acc)[G::RT], f32x16 (&accx)[G::RT]) {
-    constexpr int PF = 3;
-    f16x8 ah[2][G::RT], al[2][G::RT];
-    auto read_a = [&](int s, int set) {
-        const int tap = s / G::GPW, gg = s % G::GPW;
-        const int off = ((tap / KW) * G::HWD + tap % KW) * G::CELLB + gg * 64 * G::KS;
-#pragma unroll
-        for (int i = 0; i < G::RT; ++i) {
-            ah[set][i] = *reinterpret_cast<const f16x8 *>(abase[i] + off);
-            al[set][i] = *reinterpret_cast<const f16x8 *>(abase[i] + off + 16);
-        }
-    };
-    read_a(0, 0);
-#pragma unroll
-    for (int s = 0; s < G::STEPS; ++s) {
-        const int set = s & 1;
-        const f16x8 bh = __builtin_bit_cast(f16x8, bq[s % PF][0]), bl = __builtin_bit_cast(f16x8, bq[s % PF][1]);
-        __builtin_amdgcn_sched_barrier(0);
-        if (s + 1 < G::STEPS) read_a(s + 1, set ^ 1);
-        if (s + PF < G::STEPS) { bq[s % PF][0] = w2[(s + PF) * 128]; bq[s % PF][1] = w2[(s + PF) * 128 + 64]; }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < G::RT; ++i) acc[i] = mfma_f16(bh, ah[set][i], acc[i]);
-#pragma unroll
-        for (int i = 0; i < G::RT; ++i) accx[i] = mfma_f16(bl, ah[set][i], accx[i]);
-#pragma unroll
-        for (int i = 0; i < G::RT; ++i) accx[i] = mfma_f16(bh, al[set][i], accx[i]);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
 template <int TH, int TW, int KH, int KW>
 __global__ __launch_bounds__(512, 2) void gru_half_kernel(GruHalfArgs p) {
     using G1 = TcGeom<TH, TW, KH, KW, 256, 256>;            // the gates: wave = one 32-channel column tile of [z | r], all of K
@@ -401,14 +497,12 @@ __global__ __launch_bounds__(512, 2) void gru_half_kernel(GruHalfArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tc_lds[];
     unsigned char *lds = tc_lds;
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tile = (int)blockIdx.x;
-    const int tx_ = tile % p.tiles_x, ty_ = (tile / p.tiles_x) % p.tiles_y, img = tile / (p.tiles_x * p.tiles_y);
+    TC_TILE(p);
     // the R cells' origin, and the cells of them whose new h this workgroup writes: [olo, ohi) along the pass
     const int n_along = HORIZ ? p.tiles_x : p.tiles_y, t_along = HORIZ ? tx_ : ty_, len_along = HORIZ ? p.w : p.h;
     const int r0 = n_along > 1 ? t_along * p.step - 2 : 0;
     const int olo = n_along > 1 ? t_along * p.step : 0, ohi = n_along > 1 ? min(len_along, olo + p.step) : len_along;
     const int x0 = HORIZ ? r0 : tx_ * TW, y0 = HORIZ ? ty_ * TH : r0;
-    const long long img_base = (long long)img * p.h * p.w;
     // the context parts of this workgroup's pair: one wave-uniform load of two pointers from the table (indexed below with the
     // cell index of the whole batch, like the one-tensor form: hence the pair's offset taken off)
     const float *pre_zr = p.pre_zr, *pre_q = p.pre_q;
@@ -429,68 +523,25 @@ __global__ __launch_bounds__(512, 2) void gru_half_kernel(GruHalfArgs p) {
 #pragma unroll
     for (int s = 0; s < PF; ++s) { bq[s][0] = w1[s * 128]; bq[s][1] = w1[s * 128 + 64]; }
 
-    // ---- [h | motion] of the tile (halo included) -> LDS, 16-byte pieces, zeros outside the image
-    {
-        constexpr int PPC = 64, TOTAL = G1::HCELLS * PPC, ROUNDS = (TOTAL + 511) / 512, B = 6;
-#pragma unroll 1
-        for (int rr = 0; rr < ROUNDS; rr += B) {
-            uint4 v[B];
-#pragma unroll
-            for (int k = 0; k < B; ++k) {
-                const int q = (rr + k) * 512 + tid;
-                v[k] = make_uint4(0u, 0u, 0u, 0u);
-                if (rr + k < ROUNDS && q < TOTAL) {
-                    const int c = q / PPC, pc = q - c * PPC;
-                    const int cy = c / HWD, cx = c - cy * HWD;
-                    const int yy = y0 - KH / 2 + cy, xx = x0 - KW / 2 + cx;
-                    if (yy >= 0 && yy < p.h && xx >= 0 && xx < p.w) {
-                        const long long cell = img_base + (long long)yy * p.w + xx;
-                        const float *src = pc >= 32 ? p.mo + cell * p.ld_mo + (pc - 32) * 4 : p.h_in + cell * p.ld_hin + pc * 4;
-                        v[k] = *reinterpret_cast<const uint4 *>(src);
-                    }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < B; ++k) {
-                const int q = (rr + k) * 512 + tid;
-                if (rr + k < ROUNDS && q < TOTAL) {
-                    const int c = q / PPC, pc = q - c * PPC;
-                    *reinterpret_cast<uint4 *>(lds + c * CELLB + pc * 16) = v[k];
-                }
-            }
-        }
-    }
+    // ---- [h | motion] of the tile (halo included) -> LDS
+    TC_LOAD_TILE(G1, 64, 6, lds, tid, x0, y0, p.h, p.w, img_base,
+                 tc_piece(pc >= 32 ? p.mo + cell * p.ld_mo + (pc - 32) * 4 : p.h_in + cell * p.ld_hin + pc * 4));
     TC_T(2);
     lds_barrier();
     TC_T(3);
 
     f32x16 acc[RT], accx[RT];
     const unsigned char *abase[RT];
-    auto zero_acc = [&]() {
-#pragma unroll
-        for (int i = 0; i < RT; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[i][r] = 0.f; accx[i][r] = 0.f; }
-    };
-    auto set_abase = [&](int ks) {
-        const int r = lane & 31;
-#pragma unroll
-        for (int i = 0; i < RT; ++i) {
-            const int m = 32 * i + r;
-            abase[i] = lds + ((m / TW) * HWD + (m % TW)) * CELLB + (lane >> 5) * 32 + ks * 64;
-        }
-    };
     // an R cell's own slot in the tile: its h part is the first 512 bytes, [8 channels: hi x 8 | lo x 8] x 16
     auto slot = [&](int m) { return lds + ((m / TW + KH / 2) * HWD + (m % TW + KW / 2)) * CELLB; };
-    const float inv2048 = 1.f / 2048.f;
-    const float k2048 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(0x45000000));
+    const float k2048 = tc_k2048();
 
     // ---- z | r gates.  The r waves are the OLDER wave of every SIMD (column tile wv ^ 4: waves 0-3 take r, waves 4-7 take z): the
     // matrix pipe serves the older wave first, so it leaves this K loop ~27 k cycles before its partner (tools/gru_trace.py) -- and r is
     // the gate with work on the critical path behind it.
     const int nt1 = wv ^ 4;
-    zero_acc();
-    set_abase(0);
+    tc_zero(acc, accx);
+    TC_SET_ABASE(G1, abase, lds, lane, 0);
     tc_kloop<G1, KW>(abase, w1, bq, acc, accx);
     TC_T(4);
     // (the candidate's first weight fragments: in flight during the gate algebra)
@@ -518,9 +569,7 @@ __global__ __launch_bounds__(512, 2) void gru_half_kernel(GruHalfArgs p) {
             }
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[i][4 * b + e] + accx[i][4 * b + e] * inv2048;
+                f32x4 v = tc_sum4(acc[i], accx[i], b);
                 v += a[b];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = fast_sigmoid(v[e]);
@@ -559,31 +608,21 @@ __global__ __launch_bounds__(512, 2) void gru_half_kernel(GruHalfArgs p) {
             const int n0 = 32 * nt1 + 4 * (lane >> 5);
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[i][4 * b + e] + accx[i][4 * b + e] * inv2048;
+                const f32x4 v = tc_sum4(acc[i], accx[i], b);
                 if (own) *reinterpret_cast<f32x4 *>(p.z + cell * 128 + n0 + 8 * b) = v;
             }
         }
     }
 
     // ---- the candidate over [r * h | motion]
-    zero_acc();
-    set_abase(ks2);
+    tc_zero(acc, accx);
+    TC_SET_ABASE(G2, abase, lds, lane, ks2 * 64);
     tc_kloop<G2, KW>(abase, w2, bq, acc, accx);
     TC_T(7);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (this wave's z stores have reached L2 before anyone reads z back)
     lds_barrier();           // every wave is done with the tile: its space takes the sums
     float *red = reinterpret_cast<float *>(lds);
-#pragma unroll
-    for (int i = 0; i < RT; ++i)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            f32x4 v;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = acc[i][4 * b + e] + accx[i][4 * b + e] * inv2048;
-            *reinterpret_cast<f32x4 *>(red + (ks2 * CELLS + 32 * i + (lane & 31)) * G2::RED_ROW + 32 * nt2 + 8 * b + 4 * (lane >> 5)) = v;
-        }
+    tc_park(acc, accx, red, ks2 * CELLS, G2::RED_ROW, 32 * nt2, lane);
     lds_barrier();
     // q = tanh(. + context part), h <- (1 - z) h + z q (core/update.py:116-117, 122-123): the cells this workgroup owns
 #pragma unroll
@@ -605,15 +644,10 @@ __global__ __launch_bounds__(512, 2) void gru_half_kernel(GruHalfArgs p) {
         for (int e = 0; e < 4; ++e) { z0[e] = fast_sigmoid(z0[e]); z1[e] = fast_sigmoid(z1[e]); }
         const float *hrow = p.hf_in + cell * 128 + n0;
         const f32x4 h0 = *reinterpret_cast<const f32x4 *>(hrow), h1 = *reinterpret_cast<const f32x4 *>(hrow + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { u[e] = gru_blend(z0[e], h0[e], fast_tanh(u[e])); v[e] = gru_blend(z1[e], h1[e], fast_tanh(v[e])); }
+        tc_gru_blend8(u, v, z0, z1, h0, h1);
         *reinterpret_cast<f32x4 *>(p.hf_out + cell * 128 + n0) = u;
         *reinterpret_cast<f32x4 *>(p.hf_out + cell * 128 + n0 + 4) = v;
-        u32x4 hi, lo;
-        split8_raw(u, v, k2048, hi, lo);
-        uint4 *dst = reinterpret_cast<uint4 *>(reinterpret_cast<char *>(p.h_out + cell * p.ld_hout) + (n0 >> 3) * 32);
-        dst[0] = __builtin_bit_cast(uint4, hi);
-        dst[1] = __builtin_bit_cast(uint4, lo);
+        tc_store_split8(p.h_out + cell * p.ld_hout, n0, u, v, k2048);
     }
     TC_T(8);
     TC_CLK(1);
@@ -631,23 +665,9 @@ static int gru_half_launch(GruHalfArgs a, hipStream_t s) {
     const int n_along = along <= T ? 1 : cdiv(along, a.step);
     a.tiles_x = HORIZ ? n_along : cdiv(a.w, TW);
     a.tiles_y = HORIZ ? cdiv(a.h, TH) : n_along;
-    const long long tiles = (long long)a.P * a.tiles_x * a.tiles_y;
-    if (tiles > 0x7fffffffLL) return fail(MFTX_E_ARG, "gru_half: too many tiles");
-    auto kern = gru_half_kernel<TH, TW, KH, KW>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
-            return fail(MFTX_E_STATE, "gru_half: cannot reserve %d bytes of LDS", lds_bytes);
-        attr_set = true;
-    }
-    ProfScope prof(PC_GRU_FUSED, s, 2.0 * a.P * a.h * a.w * 384.0 * KH * KW * 256);
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(512), lds_bytes, s, a);
-    return check_launch("gru_half");
+    return tc_launch_tiles<gru_half_kernel<TH, TW, KH, KW>>("gru_half", a, lds_bytes, PC_GRU_FUSED, 2.0 * a.P * a.h * a.w * 384.0 * KH * KW * 256, s);
 }
 
-static int tc_num_cus();
-static bool tc_fills(long long tiles);
-int tile_conv_cells(int P, int h, int w, int kh);
 // tiles of the fused kernel for a pass over P maps of h x w cells with R tiles of th x tw cells
 long long gru_half_tiles(int P, int h, int w, int th, int tw, bool horiz) {
     const int along = horiz ? w : h, T = horiz ? tw : th;
@@ -659,8 +679,7 @@ int launch_gru_half(const GruHalfLaunch &d, hipStream_t s) {
     if (!d.h_in || !d.mo || !d.wzr || !d.wq || (!d.ctx && (!d.pre_zr || !d.pre_q)) || !d.z || !d.hf_in || !d.hf_out || !d.h_out) return fail(MFTX_E_ARG, "gru_half: null pointer");
     if (d.P <= 0 || d.h <= 0 || d.w <= 0 || (d.pass != 0 && d.pass != 1)) return fail(MFTX_E_ARG, "gru_half: bad sizes");
     if (d.h_in == d.h_out || d.hf_in == d.hf_out) return fail(MFTX_E_ARG, "gru_half: h is read from one buffer and written to another");
-    auto bad_split = [](const float *p, int ld) { return (reinterpret_cast<uintptr_t>(p) & 31) != 0 || (ld % 8) != 0; };
-    if (bad_split(d.h_in, d.ld_hin) || bad_split(d.mo, d.ld_mo) || bad_split(d.h_out, d.ld_hout) || !aligned16(d.wzr) || !aligned16(d.wq) ||
+    if (bad_split_row(d.h_in, d.ld_hin) || bad_split_row(d.mo, d.ld_mo) || bad_split_row(d.h_out, d.ld_hout) || !aligned16(d.wzr) || !aligned16(d.wq) ||
         !aligned16(d.pre_zr) || !aligned16(d.pre_q) || !aligned16(d.z) || !aligned16(d.hf_in) || !aligned16(d.hf_out))
         return fail(MFTX_E_ALIGN, "gru_half: split-form rows are 32-byte aligned with strides in multiples of 8; the rest 16-byte aligned");
     GruHalfArgs a{};
@@ -714,29 +733,17 @@ constexpr int OU_C = 712, OU_PASSES = 5, OU_CP = 144, OU_PROJ_ROW = 28;
 template <int TH, int TW, bool GATHER>
 __global__ __launch_bounds__(512, 2) void ou_head_kernel(OuHeadArgs p) {
     using G = TcGeom<TH, TW, 3, 3, OU_CP, 256>;
-    constexpr int RT = G::RT, CELLS = G::CELLS, PF = 3;
+    constexpr int RT = G::RT, PF = 3;
     extern __shared__ __attribute__((aligned(16))) unsigned char tc_lds[];
     unsigned char *lds = tc_lds;
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tile = (int)blockIdx.x;
-    const int tx_ = tile % p.tiles_x, ty_ = (tile / p.tiles_x) % p.tiles_y, img = tile / (p.tiles_x * p.tiles_y);
+    TC_TILE(p);
     const int x0 = tx_ * TW, y0 = ty_ * TH;
-    const long long img_base = (long long)img * p.h * p.w;
     const uint4 *__restrict__ w2 = reinterpret_cast<const uint4 *>(p.wf) + (long long)(wv * OU_PASSES * G::STEPS) * 128 + lane;
     f32x16 acc[RT], accx[RT];
-#pragma unroll
-    for (int i = 0; i < RT; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[i][r] = 0.f; accx[i][r] = 0.f; }
+    tc_zero(acc, accx);
     const unsigned char *abase[RT];
-    {
-        const int r = lane & 31;
-#pragma unroll
-        for (int i = 0; i < RT; ++i) {
-            const int m = 32 * i + r;
-            abase[i] = lds + ((m / TW) * G::HWD + (m % TW)) * G::CELLB + (lane >> 5) * 32;
-        }
-    }
+    TC_SET_ABASE(G, abase, lds, lane, 0);
 #pragma unroll 1
     for (int pass = 0; pass < OU_PASSES; ++pass) {
         uint4 bq[PF][2];
@@ -746,32 +753,10 @@ __global__ __launch_bounds__(512, 2) void ou_head_kernel(OuHeadArgs p) {
         if (pass) lds_barrier();          // every wave is done with the previous pass's channels
         // ---- channels [144 pass, 144 pass + 144) of the tile (halo included) -> LDS; zeros outside the image and past channel 712
         if constexpr (!GATHER) {
-            constexpr int PPC = OU_CP / 4, TOTAL = G::HCELLS * PPC, ROUNDS = (TOTAL + 511) / 512, B = 7;
+            constexpr int PPC = OU_CP / 4;
             const int pc_valid = pass == OU_PASSES - 1 ? (OU_C - (OU_PASSES - 1) * OU_CP) / 4 : PPC;        // 16-byte pieces that exist in this pass
-#pragma unroll 1
-            for (int rr = 0; rr < ROUNDS; rr += B) {
-                uint4 v[B];
-#pragma unroll
-                for (int k = 0; k < B; ++k) {
-                    const int q = (rr + k) * 512 + tid;
-                    v[k] = make_uint4(0u, 0u, 0u, 0u);
-                    if (rr + k < ROUNDS && q < TOTAL) {
-                        const int c = q / PPC, pc = q - c * PPC;
-                        const int cy = c / G::HWD, cx = c - cy * G::HWD;
-                        const int yy = y0 - 1 + cy, xx = x0 - 1 + cx;
-                        if (yy >= 0 && yy < p.h && xx >= 0 && xx < p.w && pc < pc_valid)
-                            v[k] = *reinterpret_cast<const uint4 *>(p.a + (img_base + (long long)yy * p.w + xx) * p.lda + pass * OU_CP + pc * 4);
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < B; ++k) {
-                    const int q = (rr + k) * 512 + tid;
-                    if (rr + k < ROUNDS && q < TOTAL) {
-                        const int c = q / PPC, pc = q - c * PPC;
-                        *reinterpret_cast<uint4 *>(lds + c * G::CELLB + pc * 16) = v[k];
-                    }
-                }
-            }
+            TC_LOAD_TILE(G, PPC, 7, lds, tid, x0, y0, p.h, p.w, img_base,
+                         pc < pc_valid ? tc_piece(p.a + cell * p.lda + pass * OU_CP + pc * 4) : make_uint4(0u, 0u, 0u, 0u));
         } else {
             // by groups of 8 channels (32 bytes of split form): group Gi = 18 pass + gl of the 90 is
             //   Gi < 32: hx[8 Gi ..] (split) | 32 <= Gi < 72: corr[8 (Gi - 32) ..] (fp32: split here) | Gi = 72: corr[320..323], flow, delta |
@@ -827,62 +812,10 @@ __global__ __launch_bounds__(512, 2) void ou_head_kernel(OuHeadArgs p) {
     lds_barrier();           // every wave is done with the input tile: its space takes the sums
 
     // ---- relu(. + bias), parked [cell][256]; then the second layers as the [256 x 27] projection (as TC_RELU_PROJ)
-    const float inv2048 = 1.f / 2048.f;
     float *red = reinterpret_cast<float *>(lds);
-#pragma unroll
-    for (int i = 0; i < RT; ++i)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            f32x4 v;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = acc[i][4 * b + e] + accx[i][4 * b + e] * inv2048;
-            *reinterpret_cast<f32x4 *>(red + (32 * i + (lane & 31)) * G::RED_ROW + 32 * wv + 8 * b + 4 * (lane >> 5)) = v;
-        }
+    tc_park(acc, accx, red, 0, G::RED_ROW, 32 * wv, lane);
     lds_barrier();
-    const float k2048 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(0x45000000));
-    const int mt = wv & 3, kh = wv >> 2;
-    const uint4 *__restrict__ wpj = reinterpret_cast<const uint4 *>(p.wproj) + lane;
-    float *tp = reinterpret_cast<float *>(lds + G::RED_BYTES);
-    if (mt < RT) {
-        f32x16 d, dx;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { d[r] = 0.f; dx[r] = 0.f; }
-        const float *xrow = red + (32 * mt + (lane & 31)) * G::RED_ROW + 8 * (lane >> 5);
-#pragma unroll
-        for (int gg = 0; gg < 8; ++gg) {
-            const int g = 8 * kh + gg;
-            f32x4 u = *reinterpret_cast<const f32x4 *>(xrow + 16 * g), v = *reinterpret_cast<const f32x4 *>(xrow + 16 * g + 4);
-            u += *reinterpret_cast<const f32x4 *>(p.bias + 16 * g + 8 * (lane >> 5));
-            v += *reinterpret_cast<const f32x4 *>(p.bias + 16 * g + 8 * (lane >> 5) + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { u[e] = relu_keep_nan(u[e]); v[e] = relu_keep_nan(v[e]); }
-            u32x4 hi, lo;
-            split8_raw(u, v, k2048, hi, lo);
-            const f16x8 wh = __builtin_bit_cast(f16x8, wpj[(g * 2) * 64]), wl = __builtin_bit_cast(f16x8, wpj[(g * 2 + 1) * 64]);
-            asm volatile("s_nop 1" : "+v"(hi), "+v"(lo));
-            const f16x8 xh = __builtin_bit_cast(f16x8, hi), xl = __builtin_bit_cast(f16x8, lo);
-            d = mfma_f16(wh, xh, d);
-            dx = mfma_f16(wl, xh, dx);
-            dx = mfma_f16(wh, xl, dx);
-        }
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int j0 = 8 * b + 4 * (lane >> 5);          // this lane's outputs j0 .. j0 + 3 of cell 32 mt + (lane & 31); 27 exist
-            if (j0 < OU_PROJ_ROW) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = d[4 * b + e] + dx[4 * b + e] * inv2048;
-                *reinterpret_cast<f32x4 *>(tp + (kh * CELLS + 32 * mt + (lane & 31)) * OU_PROJ_ROW + j0) = v;
-            }
-        }
-    }
-    lds_barrier();
-    for (int idx = tid; idx < CELLS * 27; idx += 512) {
-        const int m = idx / 27, j = idx - m * 27;
-        const int yy = y0 + m / TW, xx = x0 + m % TW;
-        if (yy < p.h && xx < p.w)
-            p.tout[(img_base + (long long)yy * p.w + xx) * 27 + j] = tp[m * OU_PROJ_ROW + j] + tp[(CELLS + m) * OU_PROJ_ROW + j];
-    }
+    tc_project<G, OU_PROJ_ROW, 27>(lds, red, p.bias, p.wproj, p.tout, x0, y0, img_base, p.h, p.w, tid, lane, wv, tc_k2048());
 }
 
 // the first layers' weight in the GEMM's packed form [>= 256 rows][9 taps][cin_pad >= 712] fp32 -> the kernel's stream
@@ -900,8 +833,7 @@ __global__ void pack_ou_head_kernel(const float *__restrict__ wpk, int cin_pad, 
     for (int e = 0; e < 4; ++e) {
         const int c = OU_CP * pass + 16 * g + 8 * (lane >> 5) + 2 * e;
         const long long base = ((long long)n * 9 + tap) * cin_pad + c;
-        const unsigned a = split_halves(c < OU_C ? wpk[base] : 0.f), b = split_halves(c + 1 < OU_C ? wpk[base + 1] : 0.f);
-        w[e] = part ? ((a >> 16) | (b & 0xffff0000u)) : ((a & 0xffffu) | (b << 16));
+        w[e] = frag_word(c < OU_C ? wpk[base] : 0.f, c + 1 < OU_C ? wpk[base + 1] : 0.f, part);
     }
     out[idx] = make_uint4(w[0], w[1], w[2], w[3]);
 }
@@ -918,8 +850,7 @@ __global__ void pack_proj27_kernel(const float *__restrict__ w2pk, uint4 *__rest
         const int k = 16 * g + 8 * (lane >> 5) + 2 * e;
         const float v0 = j < 27 ? w2pk[((long long)(j % 3) * 9 + (j / 3)) * 256 + k] : 0.f;
         const float v1 = j < 27 ? w2pk[((long long)(j % 3) * 9 + (j / 3)) * 256 + k + 1] : 0.f;
-        const unsigned a = split_halves(v0), b = split_halves(v1);
-        w[e] = part ? ((a >> 16) | (b & 0xffff0000u)) : ((a & 0xffffu) | (b << 16));
+        w[e] = frag_word(v0, v1, part);
     }
     out[idx] = make_uint4(w[0], w[1], w[2], w[3]);
 }
@@ -960,18 +891,7 @@ static int ou_head_launch(OuHeadArgs a, hipStream_t s) {
     constexpr int lds_bytes = (G::A_BYTES > G::RED_BYTES ? G::A_BYTES : G::RED_BYTES) + 2 * G::CELLS * OU_PROJ_ROW * 4;
     static_assert(G::RED_BYTES + 2 * G::CELLS * OU_PROJ_ROW * 4 <= 160 * 1024 && lds_bytes <= 160 * 1024, "ou_head: LDS");
     a.tiles_x = cdiv(a.w, TW); a.tiles_y = cdiv(a.h, TH);
-    const long long tiles = (long long)a.P * a.tiles_x * a.tiles_y;
-    if (tiles > 0x7fffffffLL) return fail(MFTX_E_ARG, "ou_heads: too many tiles");
-    auto kern = ou_head_kernel<TH, TW, GATHER>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
-            return fail(MFTX_E_STATE, "ou_heads: cannot reserve %d bytes of LDS", lds_bytes);
-        attr_set = true;
-    }
-    ProfScope prof(PC_CONV_GEMM, s, 2.0 * a.P * a.h * a.w * (256.0 * 9 * OU_C + 256.0 * 27));
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(512), lds_bytes, s, a);
-    return check_launch("ou_heads");
+    return tc_launch_tiles<ou_head_kernel<TH, TW, GATHER>>("ou_heads", a, lds_bytes, PC_CONV_GEMM, 2.0 * a.P * a.h * a.w * (256.0 * 9 * OU_C + 256.0 * 27), s);
 }
 
 // a: the heads' input [M][lda] in split form (712 channels), or null with its parts in `ga` (the engine); T: [M][27] scratch;
@@ -1021,8 +941,7 @@ __global__ void pack_tile_conv_kernel(const float *__restrict__ wpk, int taps, i
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const long long base = ((long long)n * taps + tap) * cin_pad + 16 * g + 8 * (lane >> 5) + 2 * e;
-        const unsigned a = split_halves(wpk[base]), b = split_halves(wpk[base + 1]);
-        w[e] = part ? ((a >> 16) | (b & 0xffff0000u)) : ((a & 0xffffu) | (b << 16));
+        w[e] = frag_word(wpk[base], wpk[base + 1], part);
     }
     out[idx] = make_uint4(w[0], w[1], w[2], w[3]);
 }
@@ -1042,26 +961,15 @@ template <int TH, int TW, int KH, int KW, int CIN, int N, int EPI>
 static int tc_launch(TileConvArgs a, hipStream_t s) {
     using G = TcGeom<TH, TW, KH, KW, CIN, N>;
     a.tiles_x = cdiv(a.w, TW); a.tiles_y = cdiv(a.h, TH);
-    const long long tiles = (long long)a.P * a.tiles_x * a.tiles_y;
-    if (tiles > 0x7fffffffLL) return fail(MFTX_E_ARG, "tile_conv: too many tiles");
-    auto kern = tile_conv_kernel<TH, TW, KH, KW, CIN, N, EPI>;
     constexpr int lds_bytes = G::LDS + (EPI == TC_RELU_PROJ ? G::PROJ_BYTES : 0);
     static_assert(lds_bytes <= 160 * 1024, "tile_conv: LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
-            return fail(MFTX_E_STATE, "tile_conv: cannot reserve %d bytes of LDS", lds_bytes);
-        attr_set = true;
-    }
-    ProfScope prof(PC_CONV_GEMM, s, 2.0 * a.P * a.h * a.w * ((double)N * KH * KW * CIN + (EPI == TC_RELU_PROJ ? 256.0 * 18 : 0.0)));
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(512), lds_bytes, s, a);
-    return check_launch("tile_conv");
+    return tc_launch_tiles<tile_conv_kernel<TH, TW, KH, KW, CIN, N, EPI>>("tile_conv", a, lds_bytes, PC_CONV_GEMM,
+        2.0 * a.P * a.h * a.w * ((double)N * KH * KW * CIN + (EPI == TC_RELU_PROJ ? 256.0 * 18 : 0.0)), s);
 }
 
-// tile shapes by filter and cells per tile: 3 x 3: 8 x 16 / 4 x 16 / 2 x 16; 1 x 5: 4 x 32 / 2 x 32 / 1 x 32; 5 x 1: 32 x 4 / 32 x 2 / 32 x 1
 template <int KH, int KW, int CIN, int N, int CELLS>
 static int tc_dispatch_epi(const TileConvArgs &a, int epi, hipStream_t s) {
-    constexpr int TH = KH == 3 ? CELLS / 16 : (KH == 1 ? CELLS / 32 : 32), TW = CELLS / TH;
+    constexpr int TH = tc_tile_h(KH, CELLS), TW = CELLS / TH;
     switch (epi) {
         case TC_LINEAR: return tc_launch<TH, TW, KH, KW, CIN, N, TC_LINEAR>(a, s);
         case TC_RELU: return tc_launch<TH, TW, KH, KW, CIN, N, TC_RELU>(a, s);
@@ -1080,44 +988,12 @@ bool tile_conv_applicable(int kh, int kw, int cin, int N) {
     return false;
 }
 
-// The kernel takes the time of ONE tile's K loop however few tiles there are (one workgroup per tile, one per CU): it pays
-// only when its tiles come in nearly whole rounds of the chip (>= 5/8 full) -- 7 pairs of 64 x 64 cells are 224 tiles on 256 CUs, at
-// 256 x 256 pixels (56 tiles) the ring-buffered kernel's 64 x 64 tiles are 30 % faster (bench.py, 332 vs 254 frames/s)
-static int tc_num_cus() {
-    static const int cus = [] {
-        int dev = 0, n = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) n = prop.multiProcessorCount;
-        return n;
-    }();
-    return cus;
-}
-static bool tc_fills(long long tiles) {
-    const long long cus = tc_num_cus(), rounds = (tiles + cus - 1) / cus;
-    return tiles * 8 >= rounds * cus * 5;      // >= 5/8: one refinement of 5 / 6 / 7 pairs of 64 x 64 cells is 2 / 8 / 7 % faster with them, of 4 pairs 8 % slower (tools/bench_pairs.py)
-}
-static long long tc_tiles(int P, int h, int w, int kh, int cells) {
-    const int th = kh == 3 ? cells / 16 : (kh == 1 ? cells / 32 : 32), tw = cells / th;
-    return (long long)P * cdiv(h, th) * cdiv(w, tw);
-}
-bool tile_conv_fills_chip(int P, int h, int w, int kh, int kw) { (void)kw; return tc_fills(tc_tiles(P, h, w, kh, 128)); }
-bool tile_conv_small_tiles_fill(int P, int h, int w) { return tc_tiles(P, h, w, 3, 32) * 2 >= tc_num_cus(); }
-// Cells per tile (round 4): 128 where such tiles fill the chip; else 64, else 32 -- a smaller tile is the same kernel with fewer
-// MFMA row tiles per wave: every output is the same sequence of products and sums, THE SAME BITS, so the choice may follow the
-// batch (one pair per rank of a sharded frame, a ramp-up frame, a 256 x 256 video) without a pair's result depending on it.
-int tile_conv_cells(int P, int h, int w, int kh) {
-    if (tc_fills(tc_tiles(P, h, w, kh, 128))) return 128;
-    if (tc_fills(tc_tiles(P, h, w, kh, 64)) || tc_tiles(P, h, w, kh, 64) >= tc_num_cus()) return 64;
-    return 32;
-}
-
 int launch_tile_conv(const TileConvLaunch &d, hipStream_t s) {
     if (!d.a0 || !d.wf) return fail(MFTX_E_ARG, "tile_conv: null pointer");
     if (d.P <= 0 || d.h <= 0 || d.w <= 0) return fail(MFTX_E_ARG, "tile_conv: bad sizes");
     if (!tile_conv_applicable(d.kh, d.kw, d.cin, d.N)) return fail(MFTX_E_ARG, "tile_conv: no kernel for a %d x %d convolution over %d channels, N = %d", d.kh, d.kw, d.cin, d.N);
     if (d.cin == 256 && !d.a1) return fail(MFTX_E_ARG, "tile_conv: 256 channels come as two segments of 128");
-    auto bad_split = [](const float *p, int ld) { return (reinterpret_cast<uintptr_t>(p) & 31) != 0 || (ld % 8) != 0; };
-    if (bad_split(d.a0, d.lda0) || (d.cin == 256 && bad_split(d.a1, d.lda1)) || !aligned16(d.wf) || (d.bias && !aligned16(d.bias)) ||
+    if (bad_split_row(d.a0, d.lda0) || (d.cin == 256 && bad_split_row(d.a1, d.lda1)) || !aligned16(d.wf) || (d.bias && !aligned16(d.bias)) ||
         (d.addend && (!aligned16(d.addend) || d.ld_addend % 4)))
         return fail(MFTX_E_ALIGN, "tile_conv: split-form rows are 32-byte aligned with strides in multiples of 8; weights, bias and addend 16-byte aligned");
     TileConvArgs a{};
@@ -1127,11 +1003,11 @@ int launch_tile_conv(const TileConvLaunch &d, hipStream_t s) {
     a.wproj = d.wproj; a.tout = d.tout;
     a.P = d.P; a.h = d.h; a.w = d.w;
     if (d.epi == TC_LINEAR || d.epi == TC_RELU) {
-        if (!d.out || !aligned16(d.out) || d.ldo % 4 || (d.out_split && bad_split(d.out, d.ldo))) return fail(MFTX_E_ALIGN, "tile_conv: output misaligned");
+        if (!d.out || !aligned16(d.out) || d.ldo % 4 || (d.out_split && bad_split_row(d.out, d.ldo))) return fail(MFTX_E_ALIGN, "tile_conv: output misaligned");
     } else if (d.epi == TC_GRU_ZR) {
-        if (!d.z || !d.rh || !d.hf || !aligned16(d.z) || bad_split(d.rh, 128) || !aligned16(d.hf) || d.ld_hf % 4) return fail(MFTX_E_ARG, "tile_conv: z | r epilogue operands");
+        if (!d.z || !d.rh || !d.hf || !aligned16(d.z) || bad_split_row(d.rh, 128) || !aligned16(d.hf) || d.ld_hf % 4) return fail(MFTX_E_ARG, "tile_conv: z | r epilogue operands");
     } else if (d.epi == TC_GRU_Q) {
-        if (!d.z || !d.hf || !d.hx || !aligned16(d.z) || !aligned16(d.hf) || d.ld_hf % 4 || bad_split(d.hx, d.ld_hx)) return fail(MFTX_E_ARG, "tile_conv: q epilogue operands");
+        if (!d.z || !d.hf || !d.hx || !aligned16(d.z) || !aligned16(d.hf) || d.ld_hf % 4 || bad_split_row(d.hx, d.ld_hx)) return fail(MFTX_E_ARG, "tile_conv: q epilogue operands");
     } else if (d.epi == TC_RELU_PROJ) {
         if (!d.wproj || !d.tout || !d.bias || !aligned16(d.wproj) || !aligned16(d.tout)) return fail(MFTX_E_ARG, "tile_conv: projection epilogue operands");
     } else return fail(MFTX_E_ARG, "tile_conv: unknown epilogue");
@@ -1172,25 +1048,15 @@ struct TileConv2pArgs {
 
 // load passes + K loops + parking of one wave; G: its geometry (whole K or a K half).  A function of its own, called under the
 // wave-uniform role test, so that the 128 accumulator registers of the two roles never meet in a phi (spills otherwise)
-template <class G, int TH, int TW>
+template <class G>
 __device__ __forceinline__ void tc2p_main(const TileConv2pArgs &p, unsigned char *lds, const uint4 *__restrict__ w2, int ks_off, int x0, int y0, long long img_base,
                                           float *slab, int rowf, int col0) {
     constexpr int RT = G::RT, PF = 3, PASSES = 2;
     const int tid = (int)threadIdx.x, lane = tid & 63;
     f32x16 acc[RT], accx[RT];
-#pragma unroll
-    for (int i = 0; i < RT; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[i][r] = 0.f; accx[i][r] = 0.f; }
+    tc_zero(acc, accx);
     const unsigned char *abase[RT];
-    {
-        const int r = lane & 31;
-#pragma unroll
-        for (int i = 0; i < RT; ++i) {
-            const int m = 32 * i + r;
-            abase[i] = lds + ((m / TW) * G::HWD + (m % TW)) * G::CELLB + (lane >> 5) * 32 + ks_off;
-        }
-    }
+    TC_SET_ABASE(G, abase, lds, lane, ks_off);
 #pragma unroll 1
     for (int pass = 0; pass < PASSES; ++pass) {
         const uint4 *__restrict__ wp = w2 + (long long)pass * G::STEPS * 128;
@@ -1198,48 +1064,13 @@ __device__ __forceinline__ void tc2p_main(const TileConv2pArgs &p, unsigned char
 #pragma unroll
         for (int s = 0; s < PF; ++s) { bq[s][0] = wp[s * 128]; bq[s][1] = wp[s * 128 + 64]; }      // in flight while the tile loads
         if (pass) lds_barrier();          // every wave is done with the first pass's channels
-        // ---- channels [128 pass, 128 pass + 128) of the tile (halo included) -> LDS, 16-byte pieces, zeros outside the image
-        {
-            constexpr int PPC = 32, TOTAL = G::HCELLS * PPC, ROUNDS = (TOTAL + 511) / 512, B = 8;
-#pragma unroll 1
-            for (int r0 = 0; r0 < ROUNDS; r0 += B) {
-                uint4 v[B];
-#pragma unroll
-                for (int k = 0; k < B; ++k) {
-                    const int q = (r0 + k) * 512 + tid;
-                    v[k] = make_uint4(0u, 0u, 0u, 0u);
-                    if (r0 + k < ROUNDS && q < TOTAL) {
-                        const int c = q / PPC, pc = q - c * PPC;
-                        const int cy = c / G::HWD, cx = c - cy * G::HWD;
-                        const int yy = y0 - 1 + cy, xx = x0 - 1 + cx;
-                        if (yy >= 0 && yy < p.h && xx >= 0 && xx < p.w)
-                            v[k] = *reinterpret_cast<const uint4 *>(p.a + (img_base + (long long)yy * p.w + xx) * p.lda + pass * 128 + pc * 4);
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < B; ++k) {
-                    const int q = (r0 + k) * 512 + tid;
-                    if (r0 + k < ROUNDS && q < TOTAL) {
-                        const int c = q / PPC, pc = q - c * PPC;
-                        *reinterpret_cast<uint4 *>(lds + c * G::CELLB + pc * 16) = v[k];
-                    }
-                }
-            }
-        }
+        // ---- channels [128 pass, 128 pass + 128) of the tile (halo included) -> LDS
+        TC_LOAD_TILE(G, 32, 8, lds, tid, x0, y0, p.h, p.w, img_base, tc_piece(p.a + cell * p.lda + pass * 128 + pc * 4));
         lds_barrier();
         tc_kloop<G, 3>(abase, wp, bq, acc, accx);
     }
     lds_barrier();           // every wave is done with the input tile: its space takes the sums
-    const float inv2048 = 1.f / 2048.f;
-#pragma unroll
-    for (int i = 0; i < RT; ++i)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            f32x4 v;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = acc[i][4 * b + e] + accx[i][4 * b + e] * inv2048;
-            *reinterpret_cast<f32x4 *>(slab + (32 * i + (lane & 31)) * rowf + col0 + 8 * b + 4 * (lane >> 5)) = v;
-        }
+    tc_park(acc, accx, slab, 0, rowf, col0, lane);
 }
 
 template <int TH, int TW, int N>
@@ -1253,10 +1084,8 @@ __global__ __launch_bounds__(512, 2) void tile_conv2p_kernel(TileConv2pArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tc_lds[];
     unsigned char *lds = tc_lds;
     const int tid = (int)threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tile = (int)blockIdx.x;
-    const int tx_ = tile % p.tiles_x, ty_ = (tile / p.tiles_x) % p.tiles_y, img = tile / (p.tiles_x * p.tiles_y);
+    TC_TILE(p);
     const int x0 = tx_ * TW, y0 = ty_ * TH;
-    const long long img_base = (long long)img * p.h * p.w;
     const bool full = N == 192 && wv < 4;
     const int nt = N == 128 ? (wv & 3) : (wv < 4 ? wv : 4 + ((wv - 4) >> 1));
     const int ks = N == 128 ? (wv >> 2) : (wv < 4 ? 0 : ((wv - 4) & 1));
@@ -1269,12 +1098,12 @@ __global__ __launch_bounds__(512, 2) void tile_conv2p_kernel(TileConv2pArgs p) {
     float *slab = second ? red + CELLS * RED0 : red;
     const int rowf = second ? RED1 : RED0;
     const int col0 = second && N == 192 ? 32 * (nt - 4) : 32 * nt;
-    if (N == 192 && full) tc2p_main<GF, TH, TW>(p, lds, w2, 0, x0, y0, img_base, slab, rowf, col0);
-    else tc2p_main<GH, TH, TW>(p, lds, w2, ks * 64, x0, y0, img_base, slab, rowf, col0);
+    if (N == 192 && full) tc2p_main<GF>(p, lds, w2, 0, x0, y0, img_base, slab, rowf, col0);
+    else tc2p_main<GH>(p, lds, w2, ks * 64, x0, y0, img_base, slab, rowf, col0);
     lds_barrier();
 
     // ---- row-wise epilogue: 8 consecutive channels of a cell per lane
-    const float k2048 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(0x45000000));
+    const float k2048 = tc_k2048();
     constexpr int GPC = N / 8, ITEMS = CELLS * GPC;
 #pragma unroll
     for (int it = 0; it < (ITEMS + 511) / 512; ++it) {
@@ -1303,11 +1132,9 @@ __global__ __launch_bounds__(512, 2) void tile_conv2p_kernel(TileConv2pArgs p) {
         for (int e = 0; e < 4; ++e) { u[e] = relu_keep_nan(u[e]); v[e] = relu_keep_nan(v[e]); }
         u32x4 hi, lo;
         split8_raw(u, v, k2048, hi, lo);
-        unsigned *dst = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(p.out + cell * p.ldo) + (n0 >> 3) * 32);
-        if (nv >= 8) {
-            reinterpret_cast<uint4 *>(dst)[0] = __builtin_bit_cast(uint4, hi);
-            reinterpret_cast<uint4 *>(dst)[1] = __builtin_bit_cast(uint4, lo);
-        } else {                                        // a ragged last group: whole pairs of channels only (n_valid is even)
+        if (nv >= 8) tc_store_halves8(p.out + cell * p.ldo, n0, hi, lo);
+        else {                                          // a ragged last group: whole pairs of channels only (n_valid is even)
+            unsigned *dst = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(p.out + cell * p.ldo) + (n0 >> 3) * 32);
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 if (2 * e + 1 < nv) { dst[e] = hi[e]; dst[4 + e] = lo[e]; }
@@ -1336,8 +1163,7 @@ __global__ void pack_tile_conv2p_kernel(const float *__restrict__ wpk, int cin_p
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const long long base = ((long long)n * 9 + tap) * cin_pad + 16 * g + 8 * (lane >> 5) + 2 * e;
-        const unsigned a = split_halves(wpk[base]), b = split_halves(wpk[base + 1]);
-        w[e] = part ? ((a >> 16) | (b & 0xffff0000u)) : ((a & 0xffffu) | (b << 16));
+        w[e] = frag_word(wpk[base], wpk[base + 1], part);
     }
     out[idx] = make_uint4(w[0], w[1], w[2], w[3]);
 }
@@ -1358,18 +1184,7 @@ static int tc2p_launch(TileConv2pArgs a, hipStream_t s) {
     constexpr int lds_bytes = GF::A_BYTES > red ? GF::A_BYTES : red;
     static_assert(lds_bytes <= 160 * 1024, "tile_conv2p: LDS");
     a.tiles_x = cdiv(a.w, TW); a.tiles_y = cdiv(a.h, TH);
-    const long long tiles = (long long)a.P * a.tiles_x * a.tiles_y;
-    if (tiles > 0x7fffffffLL) return fail(MFTX_E_ARG, "tile_conv2p: too many tiles");
-    auto kern = tile_conv2p_kernel<TH, TW, N>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
-            return fail(MFTX_E_STATE, "tile_conv2p: cannot reserve %d bytes of LDS", lds_bytes);
-        attr_set = true;
-    }
-    ProfScope prof(PC_CONV_GEMM, s, 2.0 * a.P * a.h * a.w * ((double)a.n_valid * 9 * 256));
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(512), lds_bytes, s, a);
-    return check_launch("tile_conv2p");
+    return tc_launch_tiles<tile_conv2p_kernel<TH, TW, N>>("tile_conv2p", a, lds_bytes, PC_CONV_GEMM, 2.0 * a.P * a.h * a.w * ((double)a.n_valid * 9 * 256), s);
 }
 
 // a [M][lda] split form, 256 channels; out [M][ldo] split form, channels [0, n_valid) written; N = 128 (n_valid <= 128, even) or 192
@@ -1379,8 +1194,7 @@ int launch_tile_conv2p(const float *a, int lda, const void *wf, const float *bia
     if (P <= 0 || h <= 0 || w <= 0) return fail(MFTX_E_ARG, "tile_conv2p: bad sizes");
     const int N = n_valid > 128 ? 192 : 128;
     if (n_valid < 8 || n_valid > 192 || (n_valid & 1) || (N == 192 && n_valid != 192)) return fail(MFTX_E_ARG, "tile_conv2p: 192 output channels, or an even number up to 128");
-    auto bad_split = [](const float *p, int ld) { return (reinterpret_cast<uintptr_t>(p) & 31) != 0 || (ld % 8) != 0; };
-    if (bad_split(a, lda) || bad_split(out, ldo) || lda < 256 || ldo < N - (N - n_valid) / 8 * 8 || !aligned16(wf) || (reinterpret_cast<uintptr_t>(bias) & 3))
+    if (bad_split_row(a, lda) || bad_split_row(out, ldo) || lda < 256 || ldo < N - (N - n_valid) / 8 * 8 || !aligned16(wf) || (reinterpret_cast<uintptr_t>(bias) & 3))
         return fail(MFTX_E_ALIGN, "tile_conv2p: split-form rows are 32-byte aligned with strides in multiples of 8; weights 16-byte aligned");
     TileConv2pArgs k{};
     k.a = a; k.lda = lda; k.wf = wf; k.bias = bias; k.out = out; k.ldo = ldo; k.n_valid = n_valid; k.P = P; k.h = h; k.w = w;
@@ -1407,8 +1221,7 @@ __global__ void pack_flow_head_kernel(const float *__restrict__ w2pk, uint4 *__r
         const int k = 16 * g + 8 * (lane >> 5) + 2 * e;
         const float v0 = j < 18 ? w2pk[((long long)(j & 1) * 9 + (j >> 1)) * 256 + k] : 0.f;
         const float v1 = j < 18 ? w2pk[((long long)(j & 1) * 9 + (j >> 1)) * 256 + k + 1] : 0.f;
-        const unsigned a = split_halves(v0), b = split_halves(v1);
-        w[e] = part ? ((a >> 16) | (b & 0xffff0000u)) : ((a & 0xffffu) | (b << 16));
+        w[e] = frag_word(v0, v1, part);
     }
     out[idx] = make_uint4(w[0], w[1], w[2], w[3]);
 }
