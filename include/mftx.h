@@ -777,6 +777,38 @@ int mftx_trackstore_tracks_from_best(const float *located, const int *cells, con
                                      int T, int H, int W, float occlusion_threshold, int columns_per_block, float *table, int *entry,
                                      void *stream);
 
+/* The video sampled along every track of a store and reduced over T columns: per template pixel the sum, the sum of squares and the
+ * count of what the video shows where the pixel is visible, relative to a reference image.  DEVICE memory throughout:
+ *   frames [T] / lohis [T] / images [T] (pointer tables, 8-byte aligned): column k is the packed frame ([H][W][4] uint16, 8-byte
+ *   aligned), its [4][2] float32 table and the video frame that belongs to it, [H][W][C] uint8, C = 1 .. 4 -- a frame may be named
+ *   by any number of columns;
+ *   reference [H][W][C] uint8, or NULL = 0 everywhere;
+ *   sum [C][H][W], sumsq [C][H][W] float32, count [H][W] int32: the results;
+ *   warped [T][H][W][C] uint8 and visible [T][H][W] uint8 (0 / 1): the per-column stack, each of them or NULL.
+ *   Images, reference, warped and visible need no alignment, sum, sumsq and count 4 bytes.
+ * Per template pixel (x, y) and column k, operation by operation in float32 without contraction:
+ *   (fx, fy, o, s) = the frame's word at the pixel, dequantised: the bits of mftx_trackstore_unpack;
+ *   px = (float)x + fx, py = (float)y + fy;
+ *   c[ch] = channel ch of images[k] at (px, py) exactly as mftx_warp_backward samples the (float)u8 plane: the same coordinate
+ *   round trip, weights and order of summation, a tap outside the frame 0;
+ *   visible = o <= occlusion_threshold && s <= sigma_max && 0 <= px <= W - 1 && 0 <= py <= H - 1 -- every comparison is false on
+ *   NaN, so a NaN flow, occlusion or sigma is never visible; sigma_max = +inf lets a +inf sigma pass;
+ *   d = c[ch] - (float)reference[y][x][ch];
+ *   where visible: sum[ch] += d, sumsq[ch] += d * d, count += 1 -- over k = 0 .. T - 1 in this order, from 0;
+ *   warped[k] = (uint8)rint(min(max(c[ch], 0), 255)), ties to even, where visible and `fill` elsewhere; visible[k] = visible.
+ * The taps' addresses are clamped into the frame: a NaN or huge position loads in-frame bytes and counts as invisible.
+ * ONE launch whatever T is: pixel blocks of 256, a lane per template pixel (lanes along x) walking all columns with 4 columns' packed
+ * words and taps in flight and the 2 C + 1 running values in registers -- no atomics, and the reduction is never split over columns.
+ * Every output element is written exactly once and nothing else is written; with warped and visible both NULL nothing is written per
+ * column.  No allocation, no copy, no synchronisation.
+ * MFTX_E_ARG: a null table, sum, sumsq or count, C outside 1 .. 4, H or W < 2, H * W >= 2^31, fill outside
+ * 0 .. 255, T < 0; MFTX_E_ALIGN: a pointer table off 8 bytes, sum, sumsq or count off 4.  T == 0: nothing is done, 0 is returned. */
+int mftx_trackstore_appearance(const uint16_t *const *frames, const float *const *lohis, const uint8_t *const *images,
+                               int T, int C, int H, int W, const uint8_t *reference /* [H][W][C] or NULL */,
+                               float occlusion_threshold, float sigma_max, int fill,
+                               float *sum /* [C][H][W] */, float *sumsq /* [C][H][W] */, int *count /* [H][W] */,
+                               uint8_t *warped /* [T][H][W][C] or NULL */, uint8_t *visible /* [T][H][W] or NULL */, void *stream);
+
 /* ---- 8f-4: frame / result transport without copy queues -------------------------------------------------------------------
  * A copy KERNEL: src -> dst, n bytes, both 16-byte aligned; either may be PINNED HOST memory (hipHostMalloc / torch
  * pin_memory: mapped into the device's address space), which a kernel reads and writes over PCIe directly.  Unlike

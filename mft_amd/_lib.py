@@ -148,6 +148,8 @@ SIGNATURES = {
                                             C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mftx_trackstore_flow_from_best": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_float, C.c_int] + [C.c_void_p] * 5),
     "mftx_trackstore_tracks_from_best": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 10 + [C.c_float, C.c_int] + [C.c_void_p] * 3),
+    "mftx_trackstore_appearance": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p, C.c_float, C.c_float, C.c_int]
+                                   + [C.c_void_p] * 6),
     "mftx_trackstore_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
     "mftx_trackstore_query": (C.c_int, [_PP, _PP, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,

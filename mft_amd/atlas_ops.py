@@ -1,8 +1,8 @@
 """Torch-tensor front end of the track atlas's per-(pixel, column) and per-(point, column) read-outs
-(``mftx_trackstore_flow_from_best``, ``mftx_trackstore_tracks_from_best``), by the contract of mft_amd/ops.py: device / dtype /
-contiguity checked, raw device pointers and the current HIP stream passed, ``MftxError`` on a non-zero return.  The host tables go
-up through ``ops._upload_tables``; stream ordering is held by tests/test_gpu_track_atlas_best.py and
-tests/test_gpu_track_atlas_points.py."""
+(``mftx_trackstore_flow_from_best``, ``mftx_trackstore_tracks_from_best``) and of the track store's read-out of the video along its
+tracks (``mftx_trackstore_appearance``), by the contract of mft_amd/ops.py: device / dtype / contiguity checked, raw device pointers
+and the current HIP stream passed, ``MftxError`` on a non-zero return.  The host tables go up through ``ops._upload_tables``; stream
+ordering is held by tests/test_gpu_track_atlas_best.py, tests/test_gpu_track_atlas_points.py and tests/test_gpu_track_appearance.py."""
 from __future__ import annotations
 
 import numpy as np
@@ -138,3 +138,54 @@ def trackstore_tracks_from_best(located, cells, group_sizes, group_candidates, r
                                                H, W, float(occlusion_threshold), int(columns_per_block), tp, ep, ops._stream()),
           "mftx_trackstore_tracks_from_best")
     return table, entry
+
+
+def trackstore_appearance(frame_ptrs, lohi_ptrs, images, reference, sum, sumsq, count, warped=None, visible=None,
+                          occlusion_threshold=0.5, sigma_max=None, fill=0):
+    """The video sampled along every track of a store and reduced over T columns, in one call (``mftx_trackstore_appearance``).
+    frame_ptrs / lohi_ptrs: HOST int64 [T], the packed frame and lohi table of each column (``ops.trackstore_slot_addresses``);
+    images: ONE uint8 device tensor [T, H, W, C] or a sequence of T uint8 device tensors [H, W, C], C = 1 .. 4, column k's video frame;
+    reference: a uint8 device tensor [H, W, C] or None (= 0).  ``sum`` / ``sumsq`` (float32 device [C, H, W]) and ``count`` (int32
+    device [H, W]) receive, per template pixel, the float32 sums over the columns in order of d = sample - reference and d * d and
+    the number of columns where the pixel is visible: occlusion <= ``occlusion_threshold``, sigma <= ``sigma_max`` (None: +inf) and
+    the position inside the frame.  ``warped`` (uint8 device [T, H, W, C]) and ``visible`` (bool device [T, H, W]), each of
+    them or None: the per-column stack, ``fill`` where not visible.  T may be 0: sums and count are zeroed.  The tables go up
+    through one pinned buffer; no host synchronisation.  Returns (sum, sumsq, count, warped, visible)."""
+    lib = _lib.load()
+    name = "trackstore_appearance"
+    frame_ptrs = np.asarray(frame_ptrs, dtype=np.int64).reshape(-1)
+    lohi_ptrs = np.asarray(lohi_ptrs, dtype=np.int64).reshape(-1)
+    T = int(frame_ptrs.shape[0])
+    if sum.dim() != 3 or tuple(sumsq.shape) != tuple(sum.shape) or tuple(count.shape) != tuple(sum.shape[1:]):
+        raise MftxError(f"{name}: sum and sumsq must be [C, H, W], count [H, W]")
+    C, H, W = (int(s) for s in sum.shape)
+    if int(lohi_ptrs.shape[0]) != T or (T and ((frame_ptrs == 0).any() or (lohi_ptrs == 0).any())):
+        raise MftxError(f"{name}: frame_ptrs and lohi_ptrs must name a stored frame for each of the T columns")
+    if isinstance(images, torch.Tensor):
+        if tuple(images.shape) != (T, H, W, C):
+            raise MftxError(f"{name}: images must be [T, H, W, C] = [{T}, {H}, {W}, {C}]")
+        first = ops._chk(images, "images", torch.uint8)
+        image_ptrs = first + np.arange(T, dtype=np.int64) * (H * W * C)
+    else:
+        images = list(images)
+        if len(images) != T or any(not isinstance(i, torch.Tensor) or tuple(i.shape) != (H, W, C) for i in images):
+            raise MftxError(f"{name}: images must be {T} tensors [H, W, C] = [{H}, {W}, {C}]")
+        image_ptrs = np.asarray([ops._chk(i, "images", torch.uint8) for i in images], dtype=np.int64)
+    if reference is not None and tuple(reference.shape) != (H, W, C):
+        raise MftxError(f"{name}: reference must be [H, W, C] = [{H}, {W}, {C}]")
+    if (warped is not None and tuple(warped.shape) != (T, H, W, C)) or (visible is not None and tuple(visible.shape) != (T, H, W)):
+        raise MftxError(f"{name}: warped must be [T, H, W, C], visible [T, H, W]")
+    if not 0 <= int(fill) <= 255:
+        raise MftxError(f"{name}: fill must be 0 .. 255")
+    rp = None if reference is None else ops._chk(reference, "reference", torch.uint8)
+    sp, qp, cp = ops._chk(sum, "sum"), ops._chk(sumsq, "sumsq"), ops._chk(count, "count", torch.int32)
+    wp = None if warped is None else ops._chk(warped, "warped", torch.uint8)
+    vp = None if visible is None else ops._chk(visible, "visible", torch.bool)
+    if T == 0:          # (nothing to send; the sums over no columns)
+        sum.zero_(), sumsq.zero_(), count.zero_()
+        return sum, sumsq, count, warped, visible
+    up, (frames, lohis, imgs) = ops._upload_tables(sum.device, (frame_ptrs, lohi_ptrs, image_ptrs), ())
+    smax = float("inf") if sigma_max is None else float(sigma_max)
+    check(lib.mftx_trackstore_appearance(frames, lohis, imgs, T, C, H, W, rp, float(occlusion_threshold), smax, int(fill), sp, qp, cp, wp, vp,
+                                         ops._stream()), "mftx_trackstore_appearance")
+    return sum, sumsq, count, warped, visible

@@ -21,6 +21,9 @@
 //            chained result has the smallest (occluded, sigma, rank) wins -- a 64-bit integer minimum in registers, one launch.
 //   tracks_from_best : that choice for sparse points given on any number of source frames, behind locate's un-reduced rows: query's
 //            tiles of 64 points x 16 columns, the candidates of a tile's source frame walked per wave, the winners out through LDS.
+//   appearance : the video read along every track -- per template pixel and column unpack's dequantisation and warp_backward's sample of
+//            the column's uint8 frame, masked by visibility and summed over the columns in order (sum, sum of squares, count; optionally
+//            the per-column stack) in one launch.
 //
 // Shared with codec.hip: quant_u16.h (block_minmax, QuantU16's enc and dec).  Shared with chain.hip: grid_sample.h (the sampler's
 // coordinate round trip, weights, order of summation, clamped taps; the host's grid_scales).
@@ -847,6 +850,131 @@ __global__ __launch_bounds__(256) void ts_tracks_best_kernel(const float4 *__res
     }
 }
 
+// ---- appearance: the video sampled along every track, reduced over the columns ---------------------------------------------------------
+// Per template pixel (x, y) and column k (a stored frame and the video frame that belongs to it, [H][W][C] uint8):
+//   (fx, fy, o, s) = the stored frame's word at the pixel, dequantised (ts_unpack_kernel's bits);  px = (float)x + fx, py = (float)y + fy;
+//   c[ch] = warp_backward_kernel's sample of the image at (px, py): grid_sample_at, the taps (float)u8, 0 outside, Bilinear::blend;
+//   visible = o <= thr && s <= sigma_max && 0 <= px <= W - 1 && 0 <= py <= H - 1     (every comparison false on NaN);
+//   d = c - (float)reference;  where visible: sum += d, sumsq += d * d, count += 1 -- over k in order, float32, no contraction.
+// A lane owns a template pixel, lanes along x: the packed words of a wave are one contiguous run of 512 bytes per column, and the taps
+// of neighbouring pixels share cache lines.  The lane walks ALL columns TAP_NF at a time: their packed words are loaded together, then
+// their samplers are set up and their 4 x C tap bytes are all in flight (clamped addresses: the loads are unconditional), then the
+// columns are reduced in order into 2 C + 1 registers -- no atomics, no LDS, and the reduction is never split over columns.  The
+// frame, lohi and image pointers and the lohi values of a column are the same for every lane (scalar loads).  STACK: per column also
+// warped = (uint8)rint(clamp(c, 0, 255)) where visible, `fill` elsewhere, and visible -- each where its pointer is not null; without it
+// nothing is written per column.
+// A group's columns beyond T read column T - 1 once more and are dropped.
+// Grid: pixel blocks of 256 -- ONE launch whatever T is.
+constexpr int TAP_NF = 4;           // columns in flight: 2, 4 and 8 were measured and time the same; the siblings' 4
+// What the pointer tables name is device memory that nothing writes while the kernel runs: said to the compiler, a pointer read from a
+// table is no generic (flat) address -- the words and the bytes are global loads, the lohi table a scalar load of constant memory.
+typedef const __attribute__((address_space(1))) unsigned long long *TapWords;       // (a packed pixel: x = the low half)
+typedef const __attribute__((address_space(1))) uint8_t *TapBytes;
+typedef const __attribute__((address_space(4))) float *TapLohi;
+
+template <int C, bool STACK>
+__global__ __launch_bounds__(256) void ts_appearance_kernel(const uint2 *const *__restrict__ frames, const float *const *__restrict__ lohis,
+                                                            const uint8_t *const *__restrict__ images, int T, int H, int W, float sx,
+                                                            float sy, const uint8_t *__restrict__ reference, float thr, float smax,
+                                                            int fill, float *__restrict__ sum, float *__restrict__ sumsq,
+                                                            int *__restrict__ count, uint8_t *__restrict__ warped,
+                                                            uint8_t *__restrict__ visible) {
+    const long long n = (long long)H * W;
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const float x = (float)(int)(p % W), y = (float)(int)(p / W);
+    const float xmax = (float)(W - 1), ymax = (float)(H - 1);
+    constexpr int NF = TAP_NF;
+    float ref[C], s[C], ss[C];
+    int cnt = 0;
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) {
+        ref[ch] = reference ? (float)reference[p * C + ch] : 0.f;
+        s[ch] = 0.f; ss[ch] = 0.f;
+    }
+    for (int t = 0; t < T; t += NF) {
+        uint2 q[NF];
+        float l[NF][8];
+        TapBytes img[NF];
+#pragma unroll
+        for (int u = 0; u < NF; ++u) {
+            const int tt = t + u < T ? t + u : T - 1;          // wave-uniform: the three pointers are scalar loads, and so is the lohi table
+            const unsigned long long word = ((TapWords)frames[tt])[p];
+            q[u] = make_uint2((unsigned)word, (unsigned)(word >> 32));
+            const TapLohi lh = (TapLohi)lohis[tt];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) l[u][k] = lh[k];
+            img[u] = (TapBytes)images[tt];
+        }
+        Bilinear w[NF];
+        bool in[NF][4], vis[NF];
+        uint8_t b[NF][4][C];
+#pragma unroll
+        for (int u = 0; u < NF; ++u) {
+            const float4 v = Dec4(l[u])(q[u]);
+            const float px = x + v.x, py = y + v.y;
+            vis[u] = v.z <= thr && v.w <= smax && px >= 0.f && px <= xmax && py >= 0.f && py <= ymax;
+            const GridSample g = grid_sample_at(px, py, sx, sy, H, W);
+            const ClampedTaps tp = clamped_taps(g, H, W);
+            w[u] = g.w;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                in[u][k] = tp.in(k);
+#pragma unroll
+                for (int ch = 0; ch < C; ++ch) b[u][k][ch] = img[u][tp.o[k] * C + ch];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < NF; ++u) {
+            if (t + u >= T) continue;
+            float c[C];
+#pragma unroll
+            for (int ch = 0; ch < C; ++ch) {
+                c[ch] = w[u].blend(in[u][0] ? (float)b[u][0][ch] : 0.f, in[u][1] ? (float)b[u][1][ch] : 0.f,
+                                   in[u][2] ? (float)b[u][2][ch] : 0.f, in[u][3] ? (float)b[u][3][ch] : 0.f);
+                const float d = c[ch] - ref[ch];
+                if (vis[u]) { s[ch] = s[ch] + d; ss[ch] = ss[ch] + d * d; }
+            }
+            if (vis[u]) ++cnt;
+            if (STACK) {
+                const long long at = (long long)(t + u) * n + p;
+#pragma unroll
+                for (int ch = 0; ch < C; ++ch) {
+                    int level = fill;
+                    if (vis[u]) level = (int)rintf(fminf(fmaxf(c[ch], 0.f), 255.f));          // (c is finite wherever the pixel is visible)
+                    if (warped) warped[at * C + ch] = (uint8_t)level;
+                }
+                if (visible) visible[at] = vis[u] ? 1 : 0;
+            }
+        }
+    }
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) { sum[ch * n + p] = s[ch]; sumsq[ch * n + p] = ss[ch]; }
+    count[p] = cnt;
+}
+
+template <int C>
+static void ts_appearance_launch(bool stack, dim3 grid, hipStream_t s, const uint2 *const *frames, const float *const *lohis,
+                                 const uint8_t *const *images, int T, int H, int W, float sx, float sy, const uint8_t *reference, float thr,
+                                 float smax, int fill, float *sum, float *sumsq, int *count, uint8_t *warped, uint8_t *visible) {
+    if (stack)
+        hipLaunchKernelGGL((ts_appearance_kernel<C, true>), grid, dim3(256), 0, s, frames, lohis, images, T, H, W, sx, sy, reference, thr,
+                           smax, fill, sum, sumsq, count, warped, visible);
+    else
+        hipLaunchKernelGGL((ts_appearance_kernel<C, false>), grid, dim3(256), 0, s, frames, lohis, images, T, H, W, sx, sy, reference, thr,
+                           smax, fill, sum, sumsq, count, warped, visible);
+}
+
+template <typename... A>
+static void ts_appearance_channels(int C, A... a) {
+    switch (C) {
+        case 1: ts_appearance_launch<1>(a...); break;
+        case 2: ts_appearance_launch<2>(a...); break;
+        case 3: ts_appearance_launch<3>(a...); break;
+        default: ts_appearance_launch<4>(a...); break;
+    }
+}
+
 static int ts_blocks(long long n) {
     const long long b = (n + (long long)TS_T * TS_PX - 1) / ((long long)TS_T * TS_PX);
     return (int)(b < 1 ? 1 : (b > TS_B_MAX ? TS_B_MAX : b));
@@ -1201,4 +1329,36 @@ extern "C" int mftx_trackstore_tracks_from_best(const float *located, const int 
                        reinterpret_cast<const uint2 *const *>(frames), lohis, G, C, Q, N, R, T, cols, H, W, sx, sy, occlusion_threshold,
                        reinterpret_cast<float4 *>(table), entry);
     return check_launch("trackstore_tracks_from_best");
+}
+
+
+extern "C" int mftx_trackstore_appearance(const uint16_t *const *frames, const float *const *lohis, const uint8_t *const *images, int T,
+                                          int C, int H, int W, const uint8_t *reference, float occlusion_threshold, float sigma_max,
+                                          int fill, float *sum, float *sumsq, int *count, uint8_t *warped, uint8_t *visible, void *stream) {
+    if (T < 0) return fail(MFTX_E_ARG, "trackstore_appearance: need T >= 0");
+    if (C < 1 || C > 4) return fail(MFTX_E_ARG, "trackstore_appearance: C = %d: need 1 .. 4 channels", C);
+    if (H < 2 || W < 2) return fail(MFTX_E_ARG, "trackstore_appearance: H and W must be >= 2");
+    if ((long long)H * W > 0x7fffffffLL) return fail(MFTX_E_ARG, "trackstore_appearance: more than 2^31 - 1 pixels");
+    if (fill < 0 || fill > 255) return fail(MFTX_E_ARG, "trackstore_appearance: fill = %d: need 0 .. 255", fill);
+    if (T == 0) return 0;
+    const struct { const void *p; const char *name; } ptrs[] = {{frames, "frames"}, {lohis, "lohis"}, {images, "images"}, {sum, "sum"},
+                                                                {sumsq, "sumsq"}, {count, "count"}};
+    for (const auto &a : ptrs)
+        if (!a.p) return fail(MFTX_E_ARG, "trackstore_appearance: null pointer: %s", a.name);
+    if (!aligned_to(frames, 8) || !aligned_to(lohis, 8) || !aligned_to(images, 8))
+        return fail(MFTX_E_ALIGN, "trackstore_appearance: the pointer tables frames, lohis and images must be 8-byte aligned");
+    if (!aligned_to(sum, 4) || !aligned_to(sumsq, 4) || !aligned_to(count, 4))
+        return fail(MFTX_E_ALIGN, "trackstore_appearance: sum, sumsq and count must be 4-byte aligned");
+    float sx, sy;
+    grid_scales(H, W, sx, sy);
+    hipStream_t s = (hipStream_t)stream;
+    const bool stack = warped != nullptr || visible != nullptr;
+    const double n = (double)H * W;
+    // per pixel and column: a packed word and (with no reuse between neighbours counted) C image bytes, with the stack C + 1 bytes out;
+    // per pixel: the reference and 8 C + 4 bytes of results
+    ProfScope prof(PC_CHAIN, s, (8.0 + C + (warped ? C : 0.0) + (visible ? 1.0 : 0.0)) * n * (double)T + (9.0 * C + 4.0) * n);
+    const dim3 grid((unsigned)(((long long)H * W + 255) / 256));
+    ts_appearance_channels(C, stack, grid, s, reinterpret_cast<const uint2 *const *>(frames), lohis, images, T, H, W, sx, sy, reference,
+                           occlusion_threshold, sigma_max, fill, sum, sumsq, count, warped, visible);
+    return check_launch("trackstore_appearance");
 }

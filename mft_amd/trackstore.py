@@ -18,6 +18,7 @@ flow that passes through its disk cache: half a quantisation step of each channe
     table, cell = store.inverse(57)                   # locate at EVERY pixel of frame 57: [H, W, 4], [H, W]
     flow, occl, sigma, found = store.results_from(57) # dense results from frame 57 to every stored frame: [T, 2, H, W], ...
     result, found = store.result_from(57, 80)         # ... one of them as a FlowOUTrackingResult
+    a = store.appearance(video, reference=video[0])   # the video read along every track: a.count, a.sum, a.sumsq, a.mean, a.var
 
 ``device="cpu"`` is a host restatement of the same operations (numpy / torch), which pins the semantics without a GPU.
 """
@@ -177,6 +178,63 @@ def chain_behind_inverse(table, q, grid, ok):
     occl = torch.where(ok, occl, one)
     sigma = torch.where(ok, sigma, inf)
     return flow.permute(1, 2, 0), occl.t(), sigma.t()
+
+
+class TrackAppearance:
+    """What ``DenseTrackStore.appearance`` returns, on the store's device.  ``count`` int32 [H, W]: the columns in which the
+    template pixel is visible; ``sum`` / ``sumsq`` float32 [C, H, W]: the sums over those columns of d = sample - reference and of
+    d * d; ``reference`` uint8 [H, W, C] or None (= 0); ``frames``: the columns' frame ids; with ``stack=True`` ``warped`` uint8
+    [T, H, W, C] and ``visible`` bool [T, H, W], else None.  ``mean`` and ``var`` are derived from them in torch."""
+
+    def __init__(self, frames, count, sum, sumsq, reference=None, warped=None, visible=None):
+        self.frames, self.count, self.sum, self.sumsq = list(frames), count, sum, sumsq
+        self.reference, self.warped, self.visible = reference, warped, visible
+
+    def _mean_d(self):
+        return (self.sum / self.count.to(torch.float32)).permute(1, 2, 0)          # 0 / 0 = NaN where the pixel was never visible
+
+    @property
+    def mean(self):
+        """float32 [H, W, C]: reference + sum / count -- the template's mean appearance over the columns where each pixel is
+        visible; NaN where count is 0."""
+        m = self._mean_d()
+        return m if self.reference is None else self.reference.to(torch.float32) + m
+
+    @property
+    def var(self):
+        """float32 [H, W, C]: max(sumsq / count - (sum / count)^2, 0); NaN where count is 0."""
+        m = self._mean_d()
+        return ((self.sumsq / self.count.to(torch.float32)).permute(1, 2, 0) - m * m).clamp(min=0)
+
+
+def _as_images(images, T, H, W, name):
+    """images: one uint8 tensor [T, H, W, C] or a sequence of T uint8 (H, W, C) numpy arrays / tensors, C = 1 .. 4 -> (the tensor,
+    or the list with numpy arrays wrapped as tensors; C).  Nothing is copied or moved.  Anything else is a ``ValueError``."""
+    def one(img, C):
+        if isinstance(img, np.ndarray):
+            if img.dtype != np.uint8:
+                raise ValueError(f"{name}: images must be uint8, not {img.dtype}")
+            img = torch.from_numpy(np.ascontiguousarray(img))
+        if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8:
+            raise ValueError(f"{name}: images must be uint8 numpy arrays or tensors")
+        if img.dim() != 3 or tuple(img.shape[:2]) != (H, W) or not 1 <= int(img.shape[2]) <= 4 or (C and int(img.shape[2]) != C):
+            raise ValueError(f"{name}: an image must be ({H}, {W}, C) with one C = 1 .. 4 for all, not {tuple(img.shape)}")
+        return img
+
+    if isinstance(images, torch.Tensor):
+        if images.dtype != torch.uint8:
+            raise ValueError(f"{name}: images must be uint8, not {images.dtype}")
+        if images.dim() != 4 or tuple(images.shape[:3]) != (T, H, W) or not 1 <= int(images.shape[3]) <= 4:
+            raise ValueError(f"{name}: images must be [{T}, {H}, {W}, C] with C = 1 .. 4, not {tuple(images.shape)}")
+        return images, int(images.shape[3])
+    images = list(images)
+    if len(images) != T:
+        raise ValueError(f"{name}: {len(images)} images for {T} frames")
+    out, C = [], 0
+    for img in images:
+        out.append(one(img, C))
+        C = int(out[-1].shape[2])
+    return out, C
 
 
 class DenseTrackStore:
@@ -479,3 +537,108 @@ class DenseTrackStore:
         their flow is NaN)."""
         flow, occl, sigma, found = self.results_from(src, [dst], occlusion_threshold)
         return FlowOUTrackingResult(flow[0], occl[0], sigma[0], validate=False), found
+
+    # ------------------------------------------------------------------ the video read along the tracks
+    def _sample_image(self, result, img, px, py):
+        """img float32 [C, H, W] sampled at (px, py) [H, W] = pixel + ``result.flow``: ``result.warp_backward(img)`` -- on the device
+        ``mftx_warp_backward``, on the host the reference's own formulation (MFT/results.py:116-136), torch's ``grid_sample``."""
+        if self.native:
+            return result.warp_backward(img)
+        from .results import _normalize_coords
+        normed = _normalize_coords(torch.stack([px, py], dim=-1)[None], self.H, self.W)
+        return torch.nn.functional.grid_sample(img[None], normed, align_corners=True)[0]
+
+    def _compose_appearance(self, slots, images, reference, occlusion_threshold, sigma_max, stack, fill):
+        """The definition of ``appearance`` as a composition, column after column, in torch on the store's device (``images`` and
+        ``reference`` are there already) -> (sum, sumsq, count, warped, visible).  The host store's path; on a device store what the
+        fused kernel is held to bit for bit (tests/test_gpu_track_appearance.py)."""
+        H, W, dev, T = self.H, self.W, self.device, len(slots)
+        C = int(images.shape[3]) if isinstance(images, torch.Tensor) else int(images[0].shape[2])
+        ref = torch.zeros((C, H, W), dtype=torch.float32, device=dev) if reference is None else reference.permute(2, 0, 1).to(torch.float32)
+        xs = torch.arange(W, dtype=torch.float32, device=dev)[None, :].expand(H, W)
+        ys = torch.arange(H, dtype=torch.float32, device=dev)[:, None].expand(H, W)
+        smax = float("inf") if sigma_max is None else float(sigma_max)
+        total, totalsq = (torch.zeros((C, H, W), dtype=torch.float32, device=dev) for _ in range(2))
+        count = torch.zeros((H, W), dtype=torch.int32, device=dev)
+        warped = torch.empty((T, H, W, C), dtype=torch.uint8, device=dev) if stack else None
+        visible = torch.empty((T, H, W), dtype=torch.bool, device=dev) if stack else None
+        zero = torch.zeros((), dtype=torch.float32, device=dev)
+        filled = torch.full((), int(fill), dtype=torch.uint8, device=dev)
+        for k, slot in enumerate(slots):
+            r = self._result_of_slot(slot)
+            px, py = xs + r.flow[0], ys + r.flow[1]
+            c = self._sample_image(r, images[k].permute(2, 0, 1).to(torch.float32).contiguous(), px, py)
+            vis = (r.occlusion[0] <= occlusion_threshold) & (r.sigma[0] <= smax) & (px >= 0) & (px <= W - 1) & (py >= 0) & (py <= H - 1)
+            d = c - ref
+            total = torch.where(vis, total + d, total)              # (d * d is a product of its own: nothing here contracts)
+            totalsq = torch.where(vis, totalsq + d * d, totalsq)
+            count += vis
+            if stack:
+                level = torch.where(vis, c, zero).clamp(0, 255).round().to(torch.uint8)           # (round: ties to even)
+                warped[k] = torch.where(vis[:, :, None], level.permute(1, 2, 0), filled)
+                visible[k] = vis
+        return total, totalsq, count, warped, visible
+
+    def appearance(self, images, frames=None, reference=None, occlusion_threshold=0.5, sigma_max=None, stack=False, fill=0):
+        """The video read along every track: per template pixel, what the frames show where the pixel goes -> ``TrackAppearance``.
+
+        frames: stored frame ids (default: all, in append order; an id may come more than once, and then counts as often);
+        images: a sequence of T images, ``images[k]`` belonging to ``frames[k]``, each (H, W, C) uint8 with C = 1 .. 4 -- numpy arrays
+        or tensors on any device (moved to the store's) -- or ONE uint8 tensor [T, H, W, C]; reference: (H, W, C) uint8, usually
+        the template frame, or None (= 0).  A ``KeyError`` for a frame that was never appended and a ``ValueError`` for a wrong
+        shape, dtype, C or fill come before any work.
+
+        For column k with r = ``result(frames[k])``, at template pixel (x, y): px = x + r.flow[0], py = y + r.flow[1];
+        c = ``r.warp_backward(images[k] as float32 [C, H, W])`` -- the bilinear sample at (px, py), 0 outside;
+        visible = (occlusion <= occlusion_threshold) & (sigma <= sigma_max) & (0 <= px <= W - 1) & (0 <= py <= H - 1), every
+        comparison false on NaN (``sigma_max=None``: +inf, which lets a +inf sigma pass); d = c - reference; and over k in the order
+        of ``frames``, in float32: sum += d, sumsq += d * d, count += 1 where visible.  With ``stack=True`` also
+        warped[k] = uint8(rint(clamp(c, 0, 255))) where visible and ``fill`` elsewhere -- the video stabilised to the template --
+        and visible[k].
+
+        The sums are taken RELATIVE to ``reference`` to keep float32 meaningful: with the template frame as the reference d is a
+        photometric residual of a few levels, whose squares sum exactly enough over hundreds of frames; raw sums of squares of
+        values up to 255 (65025 each) would leave float32 a handful of significant levels.  ``mean`` = reference + sum / count (a
+        clean plate) and ``var`` of the result are derived from them.
+
+        On the device: one table upload and ONE ``mftx_trackstore_appearance`` launch whatever T is (csrc/trackstore.hip:
+        ts_appearance_kernel: 8 + C bytes read per pixel and frame, no float stack materialised), bit for bit the composition
+        above (``_compose_appearance``); no host synchronisation when ``images`` are device tensors.  The host store runs the
+        composition with torch's ``grid_sample``: count and visible are EQUAL to the device's, the samples differ by the samplers'
+        order of operations."""
+        name = "DenseTrackStore.appearance"
+        slots = self._slots(frames)                             # KeyError before any work
+        H, W, T = self.H, self.W, len(slots)
+        images, C = _as_images(images, T, H, W, name)
+        if reference is not None:
+            if isinstance(reference, np.ndarray) and reference.dtype == np.uint8:
+                reference = torch.from_numpy(np.ascontiguousarray(reference))
+            if not isinstance(reference, torch.Tensor) or reference.dtype != torch.uint8 or reference.dim() != 3 \
+                    or tuple(reference.shape[:2]) != (H, W) or not 1 <= int(reference.shape[2]) <= 4 or (T and int(reference.shape[2]) != C):
+                raise ValueError(f"{name}: reference must be uint8 ({H}, {W}, C) with the images' C")
+            C = int(reference.shape[2])
+        if not 0 <= int(fill) <= 255:
+            raise ValueError(f"{name}: fill must be 0 .. 255")
+        C = C or 1                                              # (no image and no reference: one channel of zeros)
+        dev = self.device
+        images = images.to(dev).contiguous() if isinstance(images, torch.Tensor) else [i.to(dev).contiguous() for i in images]
+        reference = None if reference is None else reference.to(dev).contiguous()
+        ids = [self.frame_ids[s] for s in slots]
+        if T == 0:
+            z = torch.zeros((2, C, H, W), dtype=torch.float32, device=dev)
+            return TrackAppearance(ids, torch.zeros((H, W), dtype=torch.int32, device=dev), z[0], z[1], reference,
+                                   torch.zeros((0, H, W, C), dtype=torch.uint8, device=dev) if stack else None,
+                                   torch.zeros((0, H, W), dtype=torch.bool, device=dev) if stack else None)
+        if self.native:
+            from . import atlas_ops, ops
+            total, totalsq = (torch.empty((C, H, W), dtype=torch.float32, device=dev) for _ in range(2))
+            count = torch.empty((H, W), dtype=torch.int32, device=dev)
+            warped = torch.empty((T, H, W, C), dtype=torch.uint8, device=dev) if stack else None
+            visible = torch.empty((T, H, W), dtype=torch.bool, device=dev) if stack else None
+            frame_ptrs, lohi_ptrs = ops.trackstore_slot_addresses(self._chunks, self._lohi, slots)
+            atlas_ops.trackstore_appearance(frame_ptrs, lohi_ptrs, images, reference, total, totalsq, count, warped, visible,
+                                            occlusion_threshold, sigma_max, fill)
+        else:
+            total, totalsq, count, warped, visible = self._compose_appearance(slots, images, reference, occlusion_threshold, sigma_max,
+                                                                              stack, fill)
+        return TrackAppearance(ids, count, total, totalsq, reference, warped, visible)
